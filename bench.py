@@ -7,9 +7,16 @@ pure data parallel over N GPUs (weak scaling).
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
-Prints ONE JSON line on rank 0.  `roofline` is for the dominant kernel (largest total time inside the timed
-region, measured with HIP events on the launch stream); `cpu_baseline` times the oracle (numpy generator +
-PyTorch-CPU U-Net, "port" — NOT TensorFlow) on a bounded sample on rank 0 at N=1.
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the K steps and prints the headline
+(`value` = volumes/s over the wall time of the K steps, `ms_per_step` = that wall time / K).  `--full` adds what takes
+work of its own: `roofline` / `top_kernels` for the dominant kernel (largest total time inside the timed region,
+measured with per-launch HIP events on the launch stream over the last 3 timed steps), the same steps under the other
+conv arithmetic, and `cpu_baseline`, which times the oracle (numpy generator + PyTorch-CPU U-Net, "port" — NOT
+TensorFlow) on a bounded sample on rank 0 at N=1.
+
+`--dump-outputs DIR` writes, after the timed steps, what the last timed step computed (rank 0): `loss.npy` (the value
+the step returns), `params.npy` (every trainable weight after its Adam update) and `grads_sample.npy` (the step's
+gradient at 2^20 fixed, seeded positions), all float32.  The inputs depend only on the arguments.
 """
 import argparse
 import json
@@ -197,6 +204,22 @@ def cpu_worker(size, timed):
     print(json.dumps([list(step()) for _ in range(timed)]))
 
 
+DUMP_GRAD_SAMPLE = 1 << 20   # gradient entries in grads_sample.npy (4 MB; with the 53 MB of weights under 64 MB in all)
+
+
+def dump_outputs(out_dir, loss, net):
+    """--dump-outputs: what the last timed step computed -- the loss it returns, every weight after its Adam update and its
+    gradient at DUMP_GRAD_SAMPLE fixed positions drawn from a seeded generator -- as float32 DIR/<name>.npy"""
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    idx = np.sort(np.random.default_rng(0).choice(net.n_params, min(DUMP_GRAD_SAMPLE, net.n_params), replace=False))
+    arrays = {'loss': loss.detach().reshape(-1).float().cpu().numpy(),
+              'params': net.params.detach().cpu().numpy(),
+              'grads_sample': net.grads[torch.from_numpy(idx).to(net.grads.device)].cpu().numpy()}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + '.npy'), np.ascontiguousarray(a, dtype=np.float32))
+
+
 CONV_ARITH_NOTE = {
     'split': 'fp32 tensors, weights, accumulation, BatchNorm statistics and optimizer throughout; inside the 3x3x3 convs of the '
              'levels with >= 256 tiles every fp32 operand is split EXACTLY into three bf16 numbers and a product is accumulated as '
@@ -282,6 +305,11 @@ def main():
     ap.add_argument('--steps', type=int, default=100)
     ap.add_argument('--warmup', type=int, default=10)
     ap.add_argument('--size', type=int, default=160)
+    ap.add_argument('--full', action='store_true',
+                    help='also measure what the headline does not need: per-kernel figures and roofline of the last 3 timed '
+                         'steps, the other conv arithmetic, the CPU baseline')
+    ap.add_argument('--dump-outputs', default='', metavar='DIR',
+                    help='write what the last timed step computed to DIR/<name>.npy (float32)')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--cpu-size', type=int, default=160, help='volume size of the all-threads CPU baseline')
     ap.add_argument('--overlap', action='store_true', help='weight gradients on a second stream (A/B switch; slower)')
@@ -294,9 +322,10 @@ def main():
                     help='arithmetic of the fp32 convolutions (ops.set_conv_arithmetic): split = three bf16 pieces per fp32 '
                          'operand, six exact partial products on the bf16 matrix cores, fp32 accumulation; fp32_mfma = fp32 '
                          'matrix instructions everywhere')
-    ap.add_argument('--layer-table', default='', help='write the per-layer conv timings of the profiled steps to this file')
+    ap.add_argument('--layer-table', default='',
+                    help='write the per-layer conv timings of the profiled steps to this file (with --full)')
     ap.add_argument('--no-arith-compare', action='store_true',
-                    help='skip the short second measurement under the other conv arithmetic (N = 1 only, 20 steps)')
+                    help='with --full: skip the short second measurement under the other conv arithmetic (N = 1 only, 20 steps)')
     ap.add_argument('--force-allreduce', action='store_true',
                     help='initialise RCCL and run the bucketed gradient all-reduce even at world size 1 (path test)')
     ap.add_argument('--rendezvous-only', action='store_true',
@@ -306,6 +335,10 @@ def main():
 
     if args.gpus < 1:
         ap.error('--gpus must be >= 1')
+    if args.steps < 1:
+        ap.error('--steps must be >= 1')
+    if args.layer_table and not args.full:
+        ap.error('--layer-table needs --full (it is made of the profiled steps)')
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         # `python bench.py --gpus N` launched plainly: start the N ranks ourselves (one process per GPU, the way the driver's
         # torch.distributed.run command line does) instead of silently measuring one GPU under an N-GPU command
@@ -393,9 +426,9 @@ def main():
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
-    # per-launch HIP events on the LAST 3 timed steps only (0.5 ms of host / event overhead each): by then the host runs ahead of
-    # the GPU, so a region's time is what its kernels cost in a full queue, not the host's launch cadence right after a sync
-    nprof = min(3, args.steps)
+    # --full: per-launch HIP events on the LAST 3 timed steps only (0.5 ms of host / event overhead each): by then the host runs
+    # ahead of the GPU, so a region's time is what its kernels cost in a full queue, not the host's launch cadence right after a sync
+    nprof = min(3, args.steps) if args.full else 0
     # one HIP event per step boundary on the launch stream (= torch's current stream, which every kernel of the step is
     # launched on): per-step device times without a host sync inside the timed region
     marks = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]
@@ -433,9 +466,11 @@ def main():
                          step_ms_median=round(float(v[2]), 3), allreduce_wait_ms_mean=round(float(v[3]), 3),
                          allreduce_wait_ms_max=round(float(v[4]), 3)) for r, v in enumerate(allr)]
     final_loss = float(loss.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, loss, net)
     # the same steps under the OTHER conv arithmetic, same process / box / clocks (N = 1): what the split arithmetic buys
     other = None
-    if world == 1 and not args.no_arith_compare:
+    if args.full and world == 1 and not args.no_arith_compare:
         other_name = 'fp32_mfma' if args.conv_arith != 'fp32_mfma' else 'split'
         ops.set_conv_arithmetic(other_name)
         net.repack()   # re-plans and re-packs every weight set for the new arithmetic
@@ -455,7 +490,7 @@ def main():
     if not np.isfinite(final_loss):  # tf.debugging.check_numerics of the reference's IdentityLoss
         raise FloatingPointError('non-finite loss after %d steps: the measurement is invalid' % args.steps)
 
-    if rank == 0:
+    if rank == 0 and args.full:
         # per-kernel aggregation of the conv launches recorded inside the timed region
         agg, gen_agg = {}, {}
         for kind, shape, cin, cout, s, e in prof:
@@ -548,11 +583,12 @@ def main():
                                   'note': 'ms_per_volume = HIP events around the whole generator call (11 launches incl. dispatch gaps) '
                                           'on the last profiled steps; kernel_ms_sum = the kernels alone; traffic per kernel: '
                                           'profiles/pmc_traffic.json'}
+    if rank == 0:
         out = {'metric': 'training volumes/sec (160^3 fp32, 5-level U-Net)', 'value': round(world * args.steps / dt, 4),
                'unit': 'volumes/s', 'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup,
                'ms_per_step': round(1e3 * dt / args.steps, 3),
-               # per-step device times of rank 0 (HIP events at the step boundaries; the last `profiled_steps` steps carry the
-               # per-launch events of the roofline measurement): value stays K steps / wall time of the whole region
+               # per-step device times of rank 0 (HIP events at the step boundaries; with --full the last `profiled_steps` steps
+               # carry the per-launch events of the roofline measurement): value stays K steps / wall time of the whole region
                'step_ms': {'mean': round(float(step_ms.mean()), 3), 'median': round(float(np.median(step_ms)), 3),
                            'min': round(float(step_ms.min()), 3), 'max': round(float(step_ms.max()), 3),
                            'p95': round(float(np.percentile(step_ms, 95)), 3),
@@ -566,23 +602,24 @@ def main():
                           'global_batch': world, 'parallelism': 'dp%d' % world, 'volume': [S, S, S],
                           'conv_arithmetic': args.conv_arith,
                           'conv_arithmetic_note': CONV_ARITH_NOTE[args.conv_arith]},
-               'other_conv_arithmetic': other,
-               'roofline': roofline, 'roofline_generator': roofline_generator, 'final_loss': round(final_loss, 6),
+               'final_loss': round(final_loss, 6),
                'n_ranks_seen': dist.get_world_size() if dist.is_initialized() else 1,
                'backend': (backend if dist.is_initialized() else None),
                'rccl_version': rccl_version(backend) if dist.is_initialized() else None,
                # payload of the gradient all-reduce of the LAST step as the reducer issued it (expected: the whole flat
                # gradient buffer, 13 240 489 floats = 52.96 MB, in tail-first buckets)
                'allreduce_bytes_per_step': (int(tr.reducer.bytes_launched) if tr.reducer is not None and (world > 1 or args.force_allreduce) else 0),
-               'allreduce_buckets_per_step': (int(tr.reducer.n_launched) if tr.reducer is not None and (world > 1 or args.force_allreduce) else 0),
-               'top_kernels': [{k: (round(v, 4) if isinstance(v, float) else v) for k, v in r.items()} for r in rows[:6]]}
+               'allreduce_buckets_per_step': (int(tr.reducer.n_launched) if tr.reducer is not None and (world > 1 or args.force_allreduce) else 0)}
+        if args.full:
+            out.update({'other_conv_arithmetic': other, 'roofline': roofline, 'roofline_generator': roofline_generator,
+                        'top_kernels': [{k: (round(v, 4) if isinstance(v, float) else v) for k, v in r.items()} for r in rows[:6]]})
         if per_rank is not None:
             out['per_rank'] = per_rank
         elif comm_ms.size:
             out['allreduce_wait_ms'] = {'mean': round(float(comm_ms.mean()), 3), 'max': round(float(comm_ms.max()), 3)}
         if clocks:
             out['clock_log'] = clocks
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             try:
                 out['cpu_baseline'] = cpu_baseline(args.cpu_size)
             except Exception as ex:  # the baseline is a reported number, never a reason to lose the GPU measurement

@@ -8,7 +8,8 @@
 The generator runs on the GPU (its own parity is covered in test_generator_gpu.py); its image / target are copied to
 the host and pushed through oracle/unet_ref.py (PyTorch-CPU float32, autograd).  Compared: loss (1e-4 relative), every
 BatchNorm layer's batch mean / variance (5e-4 of range), the prediction (1e-3 of range) and EVERY parameter gradient
-(per-tensor max error relative to the tensor's max-abs, max-pool rounding ties aligned: 1e-3 against the fp32 oracle;
+(per-tensor max error relative to the tensor's max-abs, max-pool rounding ties aligned: 1e-3 against the fp32 oracle, plus
+that oracle's own distance from float64;
 at 160^3 also against a FLOAT64 run of the oracle: 4e-4 of range and at most 6x the fp32 oracle's own distance).  This closes "kernel variants
 chosen at the bench shape are only covered by isolated conv cases at other shapes" (VERDICT r01).
 
@@ -310,8 +311,13 @@ def test_one_training_step_at_baseline_shape_vs_oracle(S, hyperfine):
         # device vs the fp32 oracle with the max-pool ties and L1 kinks aligned (rounds 1-3 allowed 3e-3 / 3e-2 here: tie flips);
         # measured worst 3e-4 at 160^3.  At 192^3 the per-channel sums in front of a BatchNorm have almost no range of their own
         # (cancelling terms over 7 M voxels): there the bound follows from the float64 anchor of the SAME tensor -- device and fp32
-        # oracle each within (6 o + 2e-5 | o) of float64, so at most 7 o + 2e-5 apart (round 5: flat 3e-3 / 3e-2, no anchor)
-        bound = 1e-3 if not hyperfine else max(1e-3, 7.0 * anchor[nm] + 2e-5)
+        # oracle each within (6 o + 2e-5 | o) of float64, so at most 7 o + 2e-5 apart (round 5: flat 3e-3 / 3e-2, no anchor).
+        # At 160^3 the 1e-3 is a bound on the device's distance from the exact result, for which the fp32 oracle stands in; the
+        # oracle's own distance o from float64 is added.  o depends on the host: PyTorch-CPU splits the sums over the voxels
+        # into one chunk per thread: the kernel / bias gradients of the level-0 conv in front of a BatchNorm measured o = 3.7e-5 /
+        # 2.2e-4 on a 128-core host and 1.1e-3 / 1.6e-3 with 16 threads, the device 4e-5 .. 1.4e-4 on both.  The device's own
+        # distance from float64 is held to 4e-4 above
+        bound = 1e-3 + anchor[nm] if not hyperfine else max(1e-3, 7.0 * anchor[nm] + 2e-5)
         assert err < bound, 'gradient of %s: %.3e of its range (bound %.1e; worst: %s)' % (nm, err, bound, worst)
 
 

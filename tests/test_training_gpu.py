@@ -303,17 +303,22 @@ def test_training_tutorial7_residual_channel_with_reliability_maps(tmp_path):
         training(*args, work_with_residual_channel=[0, 1], **kw2)
 
 
-def test_bench_under_torchrun_with_forced_allreduce():
+def test_bench_under_torchrun_with_forced_allreduce(tmp_path):
     port = 29600 + (os.getpid() % 300)
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '1', '--master-addr',
            '127.0.0.1', '--master-port', str(port), os.path.join(REPO, 'bench.py'), '--gpus', '1', '--steps', '3',
-           '--warmup', '1', '--size', '64', '--no-cpu-baseline', '--force-allreduce']
+           '--warmup', '1', '--size', '64', '--full', '--no-cpu-baseline', '--force-allreduce', '--dump-outputs', str(tmp_path)]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=REPO)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     line = [l for l in r.stdout.splitlines() if l.startswith('{')][-1]
     d = json.loads(line)
     assert d['n_gpus'] == 1 and d['steps'] == 3 and d['value'] > 0 and np.isfinite(d['final_loss'])
     assert d['roofline']['bound'] == 'mfma' and 0 < d['roofline']['frac'] < 1
+    # --dump-outputs: the last timed step's loss, every weight, a gradient sample; float32, 64 MB at most
+    out = {n: np.load(str(tmp_path / (n + '.npy'))) for n in ('loss', 'params', 'grads_sample')}
+    assert all(a.dtype == np.float32 for a in out.values()) and sum(a.nbytes for a in out.values()) <= 64 << 20
+    assert abs(float(out['loss'][0]) - d['final_loss']) < 1e-6 and out['params'].size == 13240489
+    assert np.isfinite(out['params']).all() and np.isfinite(out['grads_sample']).all()
 
 
 def test_training_entry_point_runs_at_the_benchmark_rate(tmp_path):
