@@ -204,7 +204,11 @@ int synthsr_copy_strided(const float* in, float* out, int64_t n, int in_stride, 
 int64_t synthsr_conv3d_pack(const synthsr_conv_ctx* ctx, const float* w, float* packed, const int shape[3], int Cin, int Cout,
                             int mode, synthsr_stream_t stream);
 
-/* Conv3D 3x3x3 'same' + bias + activation (0 linear, 1 ELU alpha=1) — models.py:316,444.
+/* Conv3D 3x3x3 'same' + bias + activation (0 linear, 1 ELU alpha=1, 3 ReLU) — models.py:316,444.
+ * Activation codes of every fp32 conv entry point (synthsr_conv3d_fwd, _fwd_stats, _fwd_add, _up_fwd):
+ *   0 linear   1 ELU(alpha = 1)   2 x ELU'(addend) (_fwd_add only)   3 ReLU   4 x ReLU'(addend) (_fwd_add only)
+ * ReLU'(y) = 1 for y > 0, else 0, taken from the stored output y of the layer below (TF ReluGrad: an exact mask).
+ * These are the codes of synthsr_conv3d_bf16_fwd_ex at alpha = 0.
  * in [d0,d1,d2,Cin], out [d0,d1,d2,Cout]; wpacked from synthsr_conv3d_pack(shape,...) with the same shape.
  * For the data-gradient call it with (dout, pack(mode 1), NULL, din, shape, Cout, Cin, 0). bias may be NULL. */
 int synthsr_conv3d_fwd(const synthsr_conv_ctx* ctx, const float* in, const float* wpacked, const float* bias, float* out,
@@ -217,10 +221,11 @@ int synthsr_conv3d_fwd(const synthsr_conv_ctx* ctx, const float* in, const float
 int synthsr_conv3d_fwd_stats(const synthsr_conv_ctx* ctx, const float* in, const float* wpacked, const float* bias, float* out,
                              const int shape[3], int Cin, int Cout, int act, float* stats, double* ws, synthsr_stream_t stream);
 
-/* act 0/1: out = act(conv3(in) + addend + bias); addend is indexed like out and may alias it (in-place accumulation).
+/* act 0/1/3: out = act(conv3(in) + addend + bias); addend is indexed like out and may alias it (in-place accumulation).
  * Layers that are split over input channels (small deep levels) accumulate with atomics and require addend == out or NULL.
  * act 2 (data gradient fused with the ELU backward of the layer below): out = conv3(in) * elu'(y), y = addend != out is
- * that layer's ELU output, elu'(y) = 1 for y > 0 else y + 1 (layers.py ELU, models.py:283). */
+ * that layer's ELU output, elu'(y) = 1 for y > 0 else y + 1 (layers.py ELU, models.py:283).
+ * act 4 (the same for a ReLU network): out = conv3(in) * relu'(y), relu'(y) = 1 for y > 0 else 0. */
 int synthsr_conv3d_fwd_add(const synthsr_conv_ctx* ctx, const float* in, const float* wpacked, const float* bias,
                            const float* addend, float* out, const int shape[3], int Cin, int Cout, int act,
                            synthsr_stream_t stream);
@@ -352,7 +357,9 @@ int synthsr_conv3d_bf16_fwd(const void* in, const void* wp, const float* bias, v
                             synthsr_stream_t stream);
 int64_t synthsr_conv3d_bf16_stats_scratch(const int shape[3], int Cin, int Cout);
 /* same with the LeakyReLU epilogues of the WGAN-GP critic (SynthSR/fine_tuning_with_adversary.py:482-508):
- * act 3 = LeakyReLU(alpha), act 4 = multiply by LeakyReLU'(below) (below = the layer's activation output) */
+ * act 3 = LeakyReLU(alpha), act 4 = multiply by LeakyReLU'(below) (below = the layer's activation output); at alpha = 0
+ * these are ReLU and the fused ReLU data gradient of activation='relu' (act 3 also with stats).  act 6 = ReLU(conv3(in) + bias
+ * + below), the ReLU twin of act 5 (folded decoder; no stats). */
 int synthsr_conv3d_bf16_fwd_ex(const void* in, const void* wp, const float* bias, void* out, const int shape[3], int Cin,
                                int Cout, int act, float alpha, const void* below, float* stats, float* scratch,
                                int64_t scratch_floats, synthsr_stream_t stream);
@@ -465,6 +472,38 @@ int synthsr_bn_pool_elu_bwd(const float* dpool, const float* y, const float* dy2
 int synthsr_bn_pool_elu_bwd_bf16(const void* dpool, const void* y, const void* dy2, void* dz, float* dbias, const int shape[3],
                                  int C, const float* stats, const float* gamma, const float* beta, const float* sums, float eps,
                                  synthsr_stream_t stream);
+
+/* Activation-generic twins of the ELU-backward families above (synthsr_elu_bwd, _bn_elu_bwd, _bn_elu_bwd_head, _elu_bwd_drop,
+ * _bn_pool_elu_bwd and their bf16 twins): the same arguments and an activation code `act` in front of the stream, 1 ELU or
+ * 3 ReLU (Keras activation='relu': dz = g * (y > 0), TF ReluGrad through the stored output); any other code SYNTHSR_EINVAL.
+ * The ELU names are these entry points at act = 1. */
+int synthsr_act_bwd(const float* dy, const float* dy2, const float* y, float* dz, float* dbias, int64_t nvox, int C, int act,
+                    synthsr_stream_t stream);
+int synthsr_act_bwd_bf16(const void* dy, const void* dy2, const void* y, void* dz, float* dbias, int64_t nvox, int C, int act,
+                         synthsr_stream_t stream);
+int synthsr_bn_act_bwd(const float* dy, const float* dy2, const float* y, float* dz, float* dbias, int64_t nvox, int C,
+                       const float* stats, const float* gamma, float eps, const float* sums, int act, synthsr_stream_t stream);
+int synthsr_bn_act_bwd_bf16(const void* dy, const void* dy2, const void* y, void* dz, float* dbias, int64_t nvox, int C,
+                            const float* stats, const float* gamma, float eps, const float* sums, int act,
+                            synthsr_stream_t stream);
+int synthsr_bn_act_bwd_head(const float* dpred, const float* whead, const float* y, float* dz, float* dbias, int64_t nvox,
+                            int C, const float* stats, const float* gamma, float eps, const float* sums, int act,
+                            synthsr_stream_t stream);
+int synthsr_bn_act_bwd_head_bf16(const float* dpred, const float* whead, const void* y, void* dz, float* dbias, int64_t nvox,
+                                 int C, const float* stats, const float* gamma, float eps, const float* sums, int act,
+                                 synthsr_stream_t stream);
+int synthsr_act_bwd_drop(const float* dy, const float* dy2, const float* y, float* dz, float* dbias, int64_t nvox, int C,
+                         const float* stats, const float* gamma, float eps, const float* sums, const float* dpred,
+                         const float* whead, const float* drop, int64_t nvox_per_sample, int act, synthsr_stream_t stream);
+int synthsr_act_bwd_drop_bf16(const void* dy, const void* dy2, const void* y, void* dz, float* dbias, int64_t nvox, int C,
+                              const float* stats, const float* gamma, float eps, const float* sums, const float* dpred,
+                              const float* whead, const float* drop, int64_t nvox_per_sample, int act, synthsr_stream_t stream);
+int synthsr_bn_pool_act_bwd(const float* dpool, const float* y, const float* dy2, float* dz, float* dbias, const int shape[3],
+                            int C, const float* stats, const float* gamma, const float* beta, const float* sums, float eps,
+                            int act, synthsr_stream_t stream);
+int synthsr_bn_pool_act_bwd_bf16(const void* dpool, const void* y, const void* dy2, void* dz, float* dbias, const int shape[3],
+                                 int C, const float* stats, const float* gamma, const float* beta, const float* sums, float eps,
+                                 int act, synthsr_stream_t stream);
 /* BN backward, pass 1: sums[0..C) = sum dy, sums[C..2C) = sum dy*xhat (zeroed by caller) */
 int synthsr_bn_bwd_reduce(const float* dy, const float* x, int64_t nvox, int C, const float* stats, float eps,
                           float* sums, synthsr_stream_t stream);

@@ -52,6 +52,19 @@ __device__ __forceinline__ float elu_f(float v) {
 }
 // derivative of ELU expressed through its output y: 1 for y > 0, y + 1 (= e^x) otherwise
 __device__ __forceinline__ float elu_dy(float y) { return y > 0.f ? 1.f : y + 1.f; }
+// ReLU (act 3 / 4, Keras activation='relu'): the forward kernels take the activation family as a template parameter RELU and
+// run it under the ELU family's act codes 1 / 2 (launch_act below), so the ELU instantiations stay the code they were
+template <bool RELU>
+__device__ __forceinline__ float act_f(float v) {
+  if constexpr (RELU) return fmaxf(v, 0.f);
+  else return elu_f(v);
+}
+// derivative through the output: ReLU'(y) = 1 for y > 0, else 0 (TF ReluGrad)
+template <bool RELU>
+__device__ __forceinline__ float act_dy(float y) {
+  if constexpr (RELU) return y > 0.f ? 1.f : 0.f;
+  else return elu_dy(y);
+}
 __device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
 
 // -------------------------------------------------------------------------------------------- pack
@@ -358,7 +371,7 @@ __global__ void up_clear_kernel(float* __restrict__ dwc, int Cl, int Cout, int64
 // wave-private LDS slab so that each global store instruction writes 64 x 16 B of CONSECUTIVE addresses (a (z,y)
 // row of 16 voxels x Cout channels is contiguous in NDHWC); direct fragment stores would emit 64-byte pieces.
 // slab: 16 x (NT*16) floats.  Requires Cout % 4 == 0 (else the scalar path below).
-template <int NT, int MT>
+template <int NT, int MT, bool RELU = false>
 __device__ __forceinline__ void store_tile_rows(f32x4 (&acc)[MT][NT], float* slab, float* __restrict__ out,
                                                 const float* __restrict__ bias, const float* addend, int act, int nc,
                                                 int gz, int y0, int x0, int D1, int D2, int Cout, int lane) {
@@ -387,10 +400,10 @@ __device__ __forceinline__ void store_tile_rows(f32x4 (&acc)[MT][NT], float* sla
       const size_t o = rowoff + (size_t)x * Cout + c4 * 4;
       if (act == 2) {  // data-gradient fused with the ELU backward of the producing layer: addend = its output y
         const float4 a = *reinterpret_cast<const float4*>(addend + o);
-        v.x *= elu_dy(a.x);
-        v.y *= elu_dy(a.y);
-        v.z *= elu_dy(a.z);
-        v.w *= elu_dy(a.w);
+        v.x *= act_dy<RELU>(a.x);
+        v.y *= act_dy<RELU>(a.y);
+        v.z *= act_dy<RELU>(a.z);
+        v.w *= act_dy<RELU>(a.w);
       } else if (addend) {  // wave-uniform; may alias out (same element read and written by this lane)
         const float4 a = *reinterpret_cast<const float4*>(addend + o);
         v.x += a.x;
@@ -399,10 +412,10 @@ __device__ __forceinline__ void store_tile_rows(f32x4 (&acc)[MT][NT], float* sla
         v.w += a.w;
       }
       if (act == 1) {
-        v.x = elu_f(v.x);
-        v.y = elu_f(v.y);
-        v.z = elu_f(v.z);
-        v.w = elu_f(v.w);
+        v.x = act_f<RELU>(v.x);
+        v.y = act_f<RELU>(v.y);
+        v.z = act_f<RELU>(v.z);
+        v.w = act_f<RELU>(v.w);
       }
       *reinterpret_cast<float4*>(out + o) = v;
     }
@@ -445,7 +458,7 @@ __host__ __device__ inline uint32_t up_tapmask(int p, bool flipped) {
   return m;
 }
 
-template <int CK, int NT, int MT, bool KSPLIT, int NV>
+template <int CK, int NT, int MT, bool KSPLIT, int NV, bool RELU = false>
 __global__ __launch_bounds__(256, 2) void conv3d_fwd_kernel(const float* __restrict__ in, const float* __restrict__ wp,
                                                             const float* __restrict__ bias, float* __restrict__ out,
                                                             int D0, int D1, int D2, int Cin, int Cout, int ncc,
@@ -665,9 +678,9 @@ __global__ __launch_bounds__(256, 2) void conv3d_fwd_kernel(const float* __restr
               atomicAdd(out + oidx, acc[m][n][r]);
             } else {
               float v = acc[m][n][r] + bv;
-              if (act == 2) v *= elu_dy(ext.addend[oidx]);
+              if (act == 2) v *= act_dy<RELU>(ext.addend[oidx]);
               else if (ext.addend) v += ext.addend[oidx];
-              if (act == 1) v = elu_f(v);
+              if (act == 1) v = act_f<RELU>(v);
               out[oidx] = v;
             }
           }
@@ -685,7 +698,7 @@ __global__ __launch_bounds__(256, 2) void conv3d_fwd_kernel(const float* __restr
       for (int v = 0; v < NV; ++v) {
         float r = accv[v] + (bias ? bias[Cout - NV + v] : 0.f);
         if (ext.addend) r += ext.addend[oidx + v];
-        if (act == 1) r = elu_f(r);
+        if (act == 1) r = act_f<RELU>(r);
         out[oidx + v] = r;
       }
     }
@@ -697,7 +710,7 @@ __global__ __launch_bounds__(256, 2) void conv3d_fwd_kernel(const float* __restr
 // run on the matrix cores, the halo tile of item i+1 is fetched into registers: one 16-byte global load per tap,
 // interleaved with the B-fragment loads, so its HBM latency hides behind ~2 taps (~100 MFMAs) of compute.
 // Only the LDS store phase (2 barriers) separates two items; the output stores of an item overlap the next one.
-template <int NT>
+template <int NT, bool RELU = false>
 __global__ __launch_bounds__(256, 2) void conv3d_fwd_persist_kernel(const float* __restrict__ in,
                                                                     const float* __restrict__ wp,
                                                                     const float* __restrict__ bias,
@@ -877,7 +890,7 @@ __global__ __launch_bounds__(256, 2) void conv3d_fwd_persist_kernel(const float*
       __syncthreads();
       const int gz = z0 + wave;
       if (gz < D0)
-        store_tile_rows<NT, MT>(acc, lds + wave * (16 * NT * 16), out, bias, addend, act, nc, gz, y0, x0, D1, D2, Cout, lane);
+        store_tile_rows<NT, MT, RELU>(acc, lds + wave * (16 * NT * 16), out, bias, addend, act, nc, gz, y0, x0, D1, D2, Cout, lane);
     }
     if (!has_next) break;
     tile = ntile;
@@ -898,6 +911,7 @@ __global__ __launch_bounds__(256, 2) void conv3d_fwd_persist_kernel(const float*
 // 4 input channels, and every lane ends up with the 24 output channels of its voxel in 24 accumulator registers
 // (epilogue = 6 contiguous float4 stores per lane, no LDS transpose).  24 = 6 groups of 4: no padding.
 // Tile, halo staging and item order are those of conv3d_fwd_persist_kernel.
+template <bool RELU>
 __global__ __launch_bounds__(256, 2) void conv3d_fwd_p4_kernel(const float* __restrict__ in, const float* __restrict__ wp,
                                                                const float* __restrict__ bias, float* __restrict__ out,
                                                                int D0, int D1, int D2, int Cin, int ncc, int tiles1,
@@ -1070,10 +1084,10 @@ __global__ __launch_bounds__(256, 2) void conv3d_fwd_p4_kernel(const float* __re
           v.w += bv[4 * g + 3];
           if (act == 2) {  // fused ELU backward of the producing layer (addend = its output)
             const float4 a = *reinterpret_cast<const float4*>(addend + o + 4 * g);
-            v.x *= elu_dy(a.x);
-            v.y *= elu_dy(a.y);
-            v.z *= elu_dy(a.z);
-            v.w *= elu_dy(a.w);
+            v.x *= act_dy<RELU>(a.x);
+            v.y *= act_dy<RELU>(a.y);
+            v.z *= act_dy<RELU>(a.z);
+            v.w *= act_dy<RELU>(a.w);
           } else if (addend) {  // may alias out: same element read and written by this lane
             const float4 a = *reinterpret_cast<const float4*>(addend + o + 4 * g);
             v.x += a.x;
@@ -1082,10 +1096,10 @@ __global__ __launch_bounds__(256, 2) void conv3d_fwd_p4_kernel(const float* __re
             v.w += a.w;
           }
           if (act == 1) {
-            v.x = elu_f(v.x);
-            v.y = elu_f(v.y);
-            v.z = elu_f(v.z);
-            v.w = elu_f(v.w);
+            v.x = act_f<RELU>(v.x);
+            v.y = act_f<RELU>(v.y);
+            v.z = act_f<RELU>(v.z);
+            v.w = act_f<RELU>(v.w);
           }
           outreg[g] = v;
           if (stats_partial) {  // wave-uniform
@@ -1138,6 +1152,7 @@ __global__ __launch_bounds__(256, 2) void conv3d_fwd_p4_kernel(const float* __re
 // output parities (py, px) of one pz (4 x 6 accumulators): 4 stagings per tile instead of the 16 of the per-parity
 // launch, no padding of the 24 output channels.  items = (tile, pz, channel chunk); each lane finally stores its 4
 // hi-res voxels (2z+pz, 2y+py, 2x+px), 24 channels each.  Weights: p4 layout of the parity-combined 27-slot kernels.
+template <bool RELU>
 __global__ __launch_bounds__(256, 2) void conv3d_up_fwd_p4_kernel(const float* __restrict__ in,
                                                                   const float* __restrict__ wp,
                                                                   const float* __restrict__ bias, float* __restrict__ out,
@@ -1295,10 +1310,10 @@ __global__ __launch_bounds__(256, 2) void conv3d_up_fwd_p4_kernel(const float* _
               v.w += a.w;
             }
             if (act == 1) {
-              v.x = elu_f(v.x);
-              v.y = elu_f(v.y);
-              v.z = elu_f(v.z);
-              v.w = elu_f(v.w);
+              v.x = act_f<RELU>(v.x);
+              v.y = act_f<RELU>(v.y);
+              v.z = act_f<RELU>(v.z);
+              v.w = act_f<RELU>(v.w);
             }
             *reinterpret_cast<float4*>(out + o + 4 * g) = v;
           }
@@ -1318,7 +1333,7 @@ __global__ __launch_bounds__(256, 2) void conv3d_up_fwd_p4_kernel(const float* _
 // The generic path pads Cin = 2 to an 8-channel chunk (4x the matrix work) and is bound by everything but memory;
 // this kernel is bound by the 160^3 x 24 output write.  Lane = voxel as in conv3d_fwd_p4_kernel; the halo tile is
 // [648 voxels][Cin] in LDS (5 KB).
-template <int CIN>
+template <int CIN, bool RELU>
 __global__ __launch_bounds__(256, 2) void conv3d_fwd_c2_kernel(const float* __restrict__ in, const float* __restrict__ wp,
                                                                const float* __restrict__ bias, float* __restrict__ out,
                                                                int D0, int D1, int D2, int tiles1, int tiles2, int ntiles,
@@ -1421,10 +1436,10 @@ __global__ __launch_bounds__(256, 2) void conv3d_fwd_c2_kernel(const float* __re
         v.w += bias[4 * g + 3];
       }
       if (act == 1) {
-        v.x = elu_f(v.x);
-        v.y = elu_f(v.y);
-        v.z = elu_f(v.z);
-        v.w = elu_f(v.w);
+        v.x = act_f<RELU>(v.x);
+        v.y = act_f<RELU>(v.y);
+        v.z = act_f<RELU>(v.z);
+        v.w = act_f<RELU>(v.w);
       }
       *reinterpret_cast<float4*>(ot + lane * Cout + 4 * g) = v;
     }
@@ -1451,7 +1466,7 @@ __global__ __launch_bounds__(256, 2) void conv3d_fwd_c2_kernel(const float* __re
 //  * taps are unrolled statically (27, or the 2x2x2 window of a parity conv whose position inside the 3x3x3 stencil is a
 //    per-parity shift of the LDS base and of the scalar weight offset), so LDS reads and weight loads use immediates
 //    and the A/B fragments ping-pong between statically indexed register sets.
-template <int NT, int MT, bool KSPLIT, int NTAPS>
+template <int NT, int MT, bool KSPLIT, int NTAPS, bool RELU = false>
 __global__ __launch_bounds__(256, 2) void conv3d_fwd_lean_kernel(const float* __restrict__ in,
                                                                  const float* __restrict__ wp,
                                                                  const float* __restrict__ bias, float* __restrict__ out,
@@ -1644,9 +1659,9 @@ __global__ __launch_bounds__(256, 2) void conv3d_fwd_lean_kernel(const float* __
               atomicAdd(out + oidx, acc[m][n][r]);
             } else {
               float v = acc[m][n][r] + bv;
-              if (act == 2) v *= elu_dy(ext.addend[oidx]);
+              if (act == 2) v *= act_dy<RELU>(ext.addend[oidx]);
               else if (ext.addend) v += ext.addend[oidx];
-              if (act == 1) v = elu_f(v);
+              if (act == 1) v = act_f<RELU>(v);
               out[oidx] = v;
             }
           }
@@ -1664,7 +1679,7 @@ __global__ __launch_bounds__(256, 2) void conv3d_fwd_lean_kernel(const float* __
 // fragments), so a 64-voxel tile still carries 4 x NT x 16 output channels of work per staged halo.  The small 6x(TY+2)x6
 // halo tile makes the launch fine-grained enough for split-K to fill the chip.  Everything else (buffer-load staging with
 // hardware zero padding, static taps, register ping-pong, packed weights) is conv3d_fwd_lean_kernel's.
-template <int NT, int WM, int WN, bool KSPLIT, int NTAPS>
+template <int NT, int WM, int WN, bool KSPLIT, int NTAPS, bool RELU = false>
 __global__ __launch_bounds__(64 * WM * WN, 2) void conv3d_fwd_brick_kernel(const float* __restrict__ in,
                                                                   const float* __restrict__ wp,
                                                                   const float* __restrict__ bias, float* __restrict__ out,
@@ -1849,9 +1864,9 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void conv3d_fwd_brick_kernel(const
             atomicAdd(out + oidx, acc[m][n][r]);
           } else {
             float v = acc[m][n][r] + bv;
-            if (act == 2) v *= elu_dy(addend[oidx]);
+            if (act == 2) v *= act_dy<RELU>(addend[oidx]);
             else if (addend) v += addend[oidx];
-            if (act == 1) v = elu_f(v);
+            if (act == 1) v = act_f<RELU>(v);
             out[oidx] = v;
           }
         }
@@ -1861,12 +1876,13 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void conv3d_fwd_brick_kernel(const
 }
 
 // bias + activation after a split-K accumulation
+template <bool RELU>
 __global__ __launch_bounds__(256) void bias_act_kernel(float* __restrict__ y, const float* __restrict__ bias, int64_t n,
                                                        int C, int act, const float* __restrict__ eluy) {
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
     float v = y[i] + (bias ? bias[i % C] : 0.f);
-    if (act == 1) v = elu_f(v);
-    if (act == 2) v *= elu_dy(eluy[i]);
+    if (act == 1) v = act_f<RELU>(v);
+    if (act == 2) v *= act_dy<RELU>(eluy[i]);
     y[i] = v;
   }
 }
@@ -3137,9 +3153,17 @@ inline int parity_split(int64_t workgroups, const float* bias, int act, const Co
   return ps;
 }
 
+// act 3 / 4 (ReLU family) -> the RELU instantiation under the ELU family's codes 1 / 2; returns whether it is ReLU
+inline bool launch_act(int& act) {
+  const bool relu = act >= 3;
+  if (relu) act -= 2;
+  return relu;
+}
+
 template <int CK, int NT, int MT, bool KS, int NV = 0>
 int launch_fwd(const float* in, const float* wp, const float* bias, float* out, const int s[3], int Cin, int Cout,
                const FwdPlan& pl, int act, hipStream_t st, const ConvExt& ext) {
+  const bool relu = launch_act(act);
   const int tiles0 = cdiv(s[0], FT0), tiles1 = cdiv(s[1], MT), tiles2 = cdiv(s[2], FT2);
   const size_t smem = (size_t)FH0 * (MT + 2) * FH2 * (CK + 4) * sizeof(float);
   if constexpr (CK == 24 && NT <= 3 && NV == 0) {
@@ -3159,18 +3183,18 @@ int launch_fwd(const float* in, const float* wp, const float* bias, float* out, 
       }
       const dim3 grid(tiles0 * tiles1 * tiles2, pl.nchunks, gz);
       if (ext.mode == 0) {
-        static SynOncePerDevice done27;
-        auto k27 = conv3d_fwd_lean_kernel<NT, MT, KS, 27>;
-        if (auto once_ = done27.first()) {
+        static SynOncePerDevice done27, done27r;
+        auto k27 = relu ? conv3d_fwd_lean_kernel<NT, MT, KS, 27, true> : conv3d_fwd_lean_kernel<NT, MT, KS, 27>;
+        if (auto once_ = (relu ? done27r : done27).first()) {
           (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k27), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
         }
         hipLaunchKernelGGL(k27, grid, dim3(256), smem, st, in, wp, bias, out, s[0], s[1], s[2], Cin, Cout, pl.ncc, tiles1,
                            tiles2, act, ext);
       } else {
         if constexpr (!KS) {
-          static SynOncePerDevice done8;
-          auto k8 = conv3d_fwd_lean_kernel<NT, MT, false, 8>;
-          if (auto once_ = done8.first()) {
+          static SynOncePerDevice done8, done8r;
+          auto k8 = relu ? conv3d_fwd_lean_kernel<NT, MT, false, 8, true> : conv3d_fwd_lean_kernel<NT, MT, false, 8>;
+          if (auto once_ = (relu ? done8r : done8).first()) {
             (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k8), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
           }
           hipLaunchKernelGGL(k8, grid, dim3(256), smem, st, in, wp, bias, out, s[0], s[1], s[2], Cin, Cout, pl.ncc, tiles1,
@@ -3181,16 +3205,16 @@ int launch_fwd(const float* in, const float* wp, const float* bias, float* out, 
       }
       if (hipGetLastError() != hipSuccess) return SYNTHSR_ELAUNCH;
       if (KS && (bias != nullptr || act != 0)) {
-        hipLaunchKernelGGL(bias_act_kernel, dim3(syn_grid(nout, 256)), dim3(256), 0, st, out, bias, nout, Cout, act,
-                         act == 2 ? ext.addend : nullptr);
+        hipLaunchKernelGGL((relu ? bias_act_kernel<true> : bias_act_kernel<false>), dim3(syn_grid(nout, 256)), dim3(256), 0, st,
+                           out, bias, nout, Cout, act, act == 2 ? ext.addend : nullptr);
         if (hipGetLastError() != hipSuccess) return SYNTHSR_ELAUNCH;
       }
       return SYNTHSR_OK;
     }
   }
-  static SynOncePerDevice attr_done;
-  auto kern = conv3d_fwd_kernel<CK, NT, MT, KS, NV>;
-  if (auto once_ = attr_done.first()) {
+  static SynOncePerDevice attr_done, attr_done_r;
+  auto kern = relu ? conv3d_fwd_kernel<CK, NT, MT, KS, NV, true> : conv3d_fwd_kernel<CK, NT, MT, KS, NV>;
+  if (auto once_ = (relu ? attr_done_r : attr_done).first()) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
   }
   const int64_t nout = (int64_t)s[0] * s[1] * s[2] * Cout;
@@ -3204,8 +3228,8 @@ int launch_fwd(const float* in, const float* wp, const float* bias, float* out, 
                      s[1], s[2], Cin, Cout, pl.ncc, tiles1, tiles2, act | (PLAN_DBG << 8), ext);
   if (hipGetLastError() != hipSuccess) return SYNTHSR_ELAUNCH;
   if (KS && (bias != nullptr || act != 0)) {
-    hipLaunchKernelGGL(bias_act_kernel, dim3(syn_grid(nout, 256)), dim3(256), 0, st, out, bias, nout, Cout, act,
-                         act == 2 ? ext.addend : nullptr);
+    hipLaunchKernelGGL((relu ? bias_act_kernel<true> : bias_act_kernel<false>), dim3(syn_grid(nout, 256)), dim3(256), 0, st,
+                       out, bias, nout, Cout, act, act == 2 ? ext.addend : nullptr);
     if (hipGetLastError() != hipSuccess) return SYNTHSR_ELAUNCH;
   }
   return SYNTHSR_OK;
@@ -3214,12 +3238,13 @@ int launch_fwd(const float* in, const float* wp, const float* bias, float* out, 
 template <int NT>
 int launch_fwd_persist(const float* in, const float* wp, const float* bias, float* out, const int s[3], int Cin, int Cout,
                        const FwdPlan& pl, int act, hipStream_t st, const float* addend) {
+  const bool relu = launch_act(act);
   const int tiles0 = cdiv(s[0], FT0), tiles1 = cdiv(s[1], 4), tiles2 = cdiv(s[2], FT2);
   const int ntiles = tiles0 * tiles1 * tiles2;
   const size_t smem = (size_t)FH0 * 6 * FH2 * 28 * sizeof(float);
-  static SynOncePerDevice attr_done;
-  auto kern = conv3d_fwd_persist_kernel<NT>;
-  if (auto once_ = attr_done.first()) {
+  static SynOncePerDevice attr_done, attr_done_r;
+  auto kern = relu ? conv3d_fwd_persist_kernel<NT, true> : conv3d_fwd_persist_kernel<NT>;
+  if (auto once_ = (relu ? attr_done_r : attr_done).first()) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
   }
   int gx = 512 / pl.nchunks;  // 2 workgroups per CU in total
@@ -3233,13 +3258,14 @@ int launch_fwd_persist(const float* in, const float* wp, const float* bias, floa
 
 int launch_fwd_p4(const float* in, const float* wp, const float* bias, float* out, const int s[3], int Cin,
                   const FwdPlan& pl, int act, hipStream_t st, const float* addend, float* stats = nullptr) {
+  const bool relu = launch_act(act);
   const int tiles0 = cdiv(s[0], FT0), tiles1 = cdiv(s[1], 4), tiles2 = cdiv(s[2], FT2);
   const int ntiles = tiles0 * tiles1 * tiles2;
   const size_t smem = (size_t)FH0 * 6 * FH2 * 28 * sizeof(float);
-  static SynOncePerDevice attr_done;
-  if (auto once_ = attr_done.first()) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv3d_fwd_p4_kernel),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+  static SynOncePerDevice attr_done, attr_done_r;
+  auto kern = relu ? conv3d_fwd_p4_kernel<true> : conv3d_fwd_p4_kernel<false>;
+  if (auto once_ = (relu ? attr_done_r : attr_done).first()) {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
   }
   int gx = 512;
   while (gx > 8 && gx > ntiles) gx -= 8;
@@ -3248,7 +3274,7 @@ int launch_fwd_p4(const float* in, const float* wp, const float* bias, float* ou
     partial = ctx_scratch((size_t)gx * 48 * sizeof(float));
     if (!partial) return SYNTHSR_EWORKSPACE;
   }
-  hipLaunchKernelGGL(conv3d_fwd_p4_kernel, dim3(gx), dim3(256), smem, st, in, wp, bias, out, s[0], s[1], s[2], Cin, pl.ncc,
+  hipLaunchKernelGGL(kern, dim3(gx), dim3(256), smem, st, in, wp, bias, out, s[0], s[1], s[2], Cin, pl.ncc,
                      tiles1, tiles2, ntiles, act | (PLAN_DBG << 8), addend, partial);
   if (hipGetLastError() != hipSuccess) return SYNTHSR_ELAUNCH;
   if (stats) return synthsr_bn_stats_from_partials(partial, gx, (int64_t)s[0] * s[1] * s[2], 24, stats, st);
@@ -3258,6 +3284,7 @@ int launch_fwd_p4(const float* in, const float* wp, const float* bias, float* ou
 template <int NT, int WM, int WN, bool KS>
 int launch_fwd_brick(const float* in, const float* wp, const float* bias, float* out, const int s[3], int Cin, int Cout,
                      const FwdPlan& pl, int act, hipStream_t st, const ConvExt& ext) {
+  const bool relu = launch_act(act);
   const int tiles0 = cdiv(s[0], 4), tiles1 = cdiv(s[1], 4 * WM), tiles2 = cdiv(s[2], 4);
   const size_t smem = (size_t)6 * (4 * WM + 2) * 6 * 28 * sizeof(float);
   const int64_t nout = (int64_t)s[0] * s[1] * s[2] * Cout;
@@ -3274,20 +3301,22 @@ int launch_fwd_brick(const float* in, const float* wp, const float* bias, float*
   }
   const dim3 grid(tiles0 * tiles1 * tiles2, pl.nchunks / WN, gz);
   if (ext.mode == 0) {
-    hipLaunchKernelGGL((conv3d_fwd_brick_kernel<NT, WM, WN, KS, 27>), grid, dim3(64 * WM * WN), smem, st, in, wp, bias, out,
-                       s[0], s[1], s[2], Cin, Cout, pl.ncc, tiles1, tiles2, act, ext);
+    auto k27 = relu ? conv3d_fwd_brick_kernel<NT, WM, WN, KS, 27, true> : conv3d_fwd_brick_kernel<NT, WM, WN, KS, 27>;
+    hipLaunchKernelGGL(k27, grid, dim3(64 * WM * WN), smem, st, in, wp, bias, out, s[0], s[1], s[2], Cin, Cout, pl.ncc, tiles1,
+                       tiles2, act, ext);
   } else {
     if constexpr (!KS) {
-      hipLaunchKernelGGL((conv3d_fwd_brick_kernel<NT, WM, WN, false, 8>), grid, dim3(64 * WM * WN), smem, st, in, wp, bias,
-                         out, s[0], s[1], s[2], Cin, Cout, pl.ncc, tiles1, tiles2, act, ext);
+      auto k8 = relu ? conv3d_fwd_brick_kernel<NT, WM, WN, false, 8, true> : conv3d_fwd_brick_kernel<NT, WM, WN, false, 8>;
+      hipLaunchKernelGGL(k8, grid, dim3(64 * WM * WN), smem, st, in, wp, bias, out, s[0], s[1], s[2], Cin, Cout, pl.ncc, tiles1,
+                         tiles2, act, ext);
     } else {
       return SYNTHSR_EINVAL;
     }
   }
   if (hipGetLastError() != hipSuccess) return SYNTHSR_ELAUNCH;
   if (KS && (bias != nullptr || act != 0)) {
-    hipLaunchKernelGGL(bias_act_kernel, dim3(syn_grid(nout, 256)), dim3(256), 0, st, out, bias, nout, Cout, act,
-                       act == 2 ? addend : nullptr);
+    hipLaunchKernelGGL((relu ? bias_act_kernel<true> : bias_act_kernel<false>), dim3(syn_grid(nout, 256)), dim3(256), 0, st, out,
+                       bias, nout, Cout, act, act == 2 ? addend : nullptr);
     if (hipGetLastError() != hipSuccess) return SYNTHSR_ELAUNCH;
   }
   return SYNTHSR_OK;
@@ -3313,32 +3342,31 @@ int dispatch_fwd_brick(const float* in, const float* wp, const float* bias, floa
 
 int launch_fwd_c2(const float* in, const float* wp, const float* bias, float* out, const int s[3], int Cin, int act,
                   hipStream_t st) {
+  const bool relu = launch_act(act);
   const int tiles0 = cdiv(s[0], FT0), tiles1 = cdiv(s[1], 4), tiles2 = cdiv(s[2], FT2);
   const int ntiles = tiles0 * tiles1 * tiles2;
   int gx = 2048;  // 8 workgroups per CU: the kernel is bound by its output stores, not by the matrix cores
   while (gx > 8 && gx > ntiles) gx -= 8;
-  if (Cin == 2)
-    hipLaunchKernelGGL(conv3d_fwd_c2_kernel<2>, dim3(gx), dim3(256), 0, st, in, wp, bias, out, s[0], s[1], s[2], tiles1,
-                       tiles2, ntiles, act);
-  else
-    hipLaunchKernelGGL(conv3d_fwd_c2_kernel<1>, dim3(gx), dim3(256), 0, st, in, wp, bias, out, s[0], s[1], s[2], tiles1,
-                       tiles2, ntiles, act);
+  auto kern = Cin == 2 ? (relu ? conv3d_fwd_c2_kernel<2, true> : conv3d_fwd_c2_kernel<2, false>)
+                        : (relu ? conv3d_fwd_c2_kernel<1, true> : conv3d_fwd_c2_kernel<1, false>);
+  hipLaunchKernelGGL(kern, dim3(gx), dim3(256), 0, st, in, wp, bias, out, s[0], s[1], s[2], tiles1, tiles2, ntiles, act);
   return hipGetLastError() == hipSuccess ? SYNTHSR_OK : SYNTHSR_ELAUNCH;
 }
 
 int launch_up_fwd_p4(const float* in, const float* wp, const float* bias, float* out, const int s[3], int Cin,
                      const FwdPlan& pl, int act, hipStream_t st, int64_t wstride, const float* addend) {
+  const bool relu = launch_act(act);
   const int tiles0 = cdiv(s[0], FT0), tiles1 = cdiv(s[1], 4), tiles2 = cdiv(s[2], FT2);
   const int ntiles = tiles0 * tiles1 * tiles2;
   const size_t smem = (size_t)FH0 * 6 * FH2 * 28 * sizeof(float);
-  static SynOncePerDevice attr_done;
-  if (auto once_ = attr_done.first()) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv3d_up_fwd_p4_kernel),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+  static SynOncePerDevice attr_done, attr_done_r;
+  auto kern = relu ? conv3d_up_fwd_p4_kernel<true> : conv3d_up_fwd_p4_kernel<false>;
+  if (auto once_ = (relu ? attr_done_r : attr_done).first()) {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
   }
   int gx = 512;
   while (gx > 8 && gx > ntiles) gx -= 8;
-  hipLaunchKernelGGL(conv3d_up_fwd_p4_kernel, dim3(gx), dim3(256), smem, st, in, wp, bias, out, s[0], s[1], s[2], Cin,
+  hipLaunchKernelGGL(kern, dim3(gx), dim3(256), smem, st, in, wp, bias, out, s[0], s[1], s[2], Cin,
                      pl.ncc, tiles1, tiles2, ntiles, act, wstride, addend);
   return hipGetLastError() == hipSuccess ? SYNTHSR_OK : SYNTHSR_ELAUNCH;
 }
@@ -3927,7 +3955,7 @@ int synthsr_conv3d_fwd(const synthsr_conv_ctx* ctx, const float* in, const float
   const CtxScope scope(ctx);
   if (!scope.ok) return SYNTHSR_EINVAL;
   if (!in || !wpacked || !out || !shape || Cin < 1 || Cout < 1 || shape[0] < 1 || shape[1] < 1 || shape[2] < 1 ||
-      (act != 0 && act != 1))
+      (act != 0 && act != 1 && act != 3))
     return SYNTHSR_EINVAL;
   const FwdPlan pl = plan_fwd(shape, Cin, Cout);
   if (pl.split)
@@ -3945,7 +3973,7 @@ int synthsr_conv3d_fwd_add(const synthsr_conv_ctx* ctx, const float* in, const f
   const CtxScope scope(ctx);
   if (!scope.ok) return SYNTHSR_EINVAL;
   if (!in || !wpacked || !out || !shape || Cin < 1 || Cout < 1 || shape[0] < 1 || shape[1] < 1 || shape[2] < 1 ||
-      (act != 0 && act != 1 && act != 2) || (act == 2 && (!addend || addend == out)))
+      act < 0 || act > 4 || ((act == 2 || act == 4) && (!addend || addend == out)))
     return SYNTHSR_EINVAL;
   const FwdPlan pl = plan_fwd(shape, Cin, Cout);
   if (pl.split)
@@ -3962,7 +3990,7 @@ int synthsr_conv3d_fwd_stats(const synthsr_conv_ctx* ctx, const float* in, const
   const CtxScope scope(ctx);
   if (!scope.ok) return SYNTHSR_EINVAL;
   if (!in || !wpacked || !out || !shape || !stats || !ws || Cin < 1 || Cout < 1 || shape[0] < 1 || shape[1] < 1 ||
-      shape[2] < 1 || (act != 0 && act != 1))
+      shape[2] < 1 || (act != 0 && act != 1 && act != 3))
     return SYNTHSR_EINVAL;
   const int64_t nvox = (int64_t)shape[0] * shape[1] * shape[2];
   const FwdPlan pl = plan_fwd(shape, Cin, Cout);
@@ -3985,7 +4013,7 @@ int synthsr_conv3d_up_fwd(const synthsr_conv_ctx* ctx, const float* lo, const fl
   const CtxScope scope(ctx);
   if (!scope.ok) return SYNTHSR_EINVAL;
   if (!lo || !wpacked8 || !out || !lo_shape || Cl < 1 || Cout < 1 || lo_shape[0] < 1 || lo_shape[1] < 1 ||
-      lo_shape[2] < 1 || (act != 0 && act != 1))
+      lo_shape[2] < 1 || (act != 0 && act != 1 && act != 3))
     return SYNTHSR_EINVAL;
   const FwdPlan pl = plan_fwd(lo_shape, Cl, Cout, 2);
   if (pl.split)  // all parities from one converted low-resolution halo (conv_split.hip: conv3d_split_upfwd_kernel)

@@ -106,6 +106,13 @@ __device__ __forceinline__ float elu_f(float v) {
   return v > 0.f ? v : e;
 }
 __device__ __forceinline__ float elu_dy(float y) { return y > 0.f ? 1.f : y + 1.f; }
+// act 6 = ReLU(conv + bias + addend), the ReLU twin of act 5: the kernels' RELU instantiation runs it as act 5 with this function,
+// so the ELU instantiation stays the code it was (act 3 / 4 with alpha = 0 are ReLU and ReLU' already)
+template <bool RELU>
+__device__ __forceinline__ float act5_f(float v) {
+  if constexpr (RELU) return fmaxf(v, 0.f);
+  else return elu_f(v);
+}
 
 __device__ __forceinline__ uint32_t f2bf(float f) {  // round to nearest even (finite inputs)
   uint32_t u = __float_as_uint(f);
@@ -228,7 +235,7 @@ struct FwdArgs {
 //         skip-channel conv then adds them in its epilogue, act 5);
 //   UPM 2 (data gradient): `in` = dz on the 2x grid; the 8 parities are K chunks (cc = parity * ncc_real + chunk): parity p
 //         stages the sub-lattice dz[2 v + p] and multiplies by its transposed 8-tap set; output = d(lo) on the low-res grid.
-template <int CK, int MT, bool WLDS, int UPM = 0>
+template <int CK, int MT, bool WLDS, int UPM = 0, bool RELU = false>
 __global__ __launch_bounds__(256, 2) void conv3d_bf16_fwd_kernel(const FwdArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
   constexpr int C8 = CK / 8, ROWB = rowb_fwd(CK), NTAPS = UPM ? 8 : 27, NSTEP = (NTAPS * C8 + 3) / 4;
@@ -325,7 +332,8 @@ __global__ __launch_bounds__(256, 2) void conv3d_bf16_fwd_kernel(const FwdArgs a
 
   // epilogue through buffer instructions when the output fits 32-bit byte offsets
   const int64_t out_bytes = (int64_t)(UPM == 1 ? 8 : 1) * D0 * D1 * D2 * Cout * 2;
-  const bool fast_epi = !a.partial && out_bytes < (1ll << 31) && (!a.stats_partial || a.act <= 1);
+  // (the RELU instantiation runs act 6 as act 5 and act 3 with statistics: both have a compile-time case below)
+  const bool fast_epi = !a.partial && out_bytes < (1ll << 31) && (RELU || !a.stats_partial || a.act <= 1);
   const __amdgpu_buffer_rsrc_t rout = __builtin_amdgcn_make_buffer_rsrc(a.out, 0, (int)(fast_epi ? out_bytes : 0), 0x00020000);
   const __amdgpu_buffer_rsrc_t rbelow = __builtin_amdgcn_make_buffer_rsrc(
       const_cast<bf16_t*>(a.below ? a.below : a.out), 0, (int)(fast_epi ? out_bytes : 0), 0x00020000);
@@ -451,10 +459,10 @@ __global__ __launch_bounds__(256, 2) void conv3d_bf16_fwd_kernel(const FwdArgs a
               v[3] *= bf2f(b.y >> 16) > 0.f ? 1.f : a.alpha;
             } else if constexpr (ACT == 5) {  // ELU(conv + bias + addend): the other channel range's partial sums (folding)
               const u32x2 b = __builtin_amdgcn_raw_buffer_load_b64(rbelow, (int)off, 0, 0);
-              v[0] = elu_f(v[0] + bf2f(b.x & 0xffffu));
-              v[1] = elu_f(v[1] + bf2f(b.x >> 16));
-              v[2] = elu_f(v[2] + bf2f(b.y & 0xffffu));
-              v[3] = elu_f(v[3] + bf2f(b.y >> 16));
+              v[0] = act5_f<RELU>(v[0] + bf2f(b.x & 0xffffu));
+              v[1] = act5_f<RELU>(v[1] + bf2f(b.x >> 16));
+              v[2] = act5_f<RELU>(v[2] + bf2f(b.y & 0xffffu));
+              v[3] = act5_f<RELU>(v[3] + bf2f(b.y >> 16));
             }
             u32x2 o;
             o.x = pack2(v[0], v[1]);
@@ -472,7 +480,10 @@ __global__ __launch_bounds__(256, 2) void conv3d_bf16_fwd_kernel(const FwdArgs a
       };
       using T_ = std::true_type;
       using F_ = std::false_type;
-      if (a.stats_partial) {
+      if constexpr (RELU) {  // ReLU with statistics (act 3, alpha = 0), or ReLU(conv + bias + addend) (act 6 -> 5)
+        if (a.stats_partial) epi(std::integral_constant<int, 3>{}, T_{});
+        else epi(std::integral_constant<int, 5>{}, F_{});
+      } else if (a.stats_partial) {
         if (a.act == 1) epi(std::integral_constant<int, 1>{}, T_{});
         else epi(std::integral_constant<int, 0>{}, T_{});
       } else if (a.act == 0) epi(std::integral_constant<int, 0>{}, F_{});
@@ -521,10 +532,10 @@ __global__ __launch_bounds__(256, 2) void conv3d_bf16_fwd_kernel(const FwdArgs a
           v[3] *= bf2f(b.y >> 16) > 0.f ? 1.f : a.alpha;
         } else if (a.act == 5) {
           const u32x2 b = *reinterpret_cast<const u32x2*>(a.below + vox * Cout + co);
-          v[0] = elu_f(v[0] + bf2f(b.x & 0xffffu));
-          v[1] = elu_f(v[1] + bf2f(b.x >> 16));
-          v[2] = elu_f(v[2] + bf2f(b.y & 0xffffu));
-          v[3] = elu_f(v[3] + bf2f(b.y >> 16));
+          v[0] = act5_f<RELU>(v[0] + bf2f(b.x & 0xffffu));
+          v[1] = act5_f<RELU>(v[1] + bf2f(b.x >> 16));
+          v[2] = act5_f<RELU>(v[2] + bf2f(b.y & 0xffffu));
+          v[3] = act5_f<RELU>(v[3] + bf2f(b.y >> 16));
         }
         u32x2 o;
         o.x = pack2(v[0], v[1]);
@@ -566,16 +577,20 @@ __global__ __launch_bounds__(256, 2) void conv3d_bf16_fwd_kernel(const FwdArgs a
 }
 
 template <int CK, int MT, bool WLDS>
-int launch_fwd_w(const FwdArgs& a, int nchunks, hipStream_t st) {
+int launch_fwd_w(const FwdArgs& a0, int nchunks, hipStream_t st) {
   int gx = 512;
-  while (gx > 8 && gx - 8 >= a.ntiles) gx -= 8;  // never narrower than the tile count: a second tile doubles a straggler's time
-  if (a.ntiles < 8) gx = a.ntiles;
+  while (gx > 8 && gx - 8 >= a0.ntiles) gx -= 8;  // never narrower than the tile count: a second tile doubles a straggler's time
+  if (a0.ntiles < 8) gx = a0.ntiles;
   constexpr int NSTEP = (27 * (CK / 8) + 3) / 4;
   const size_t hbytes = ((size_t)HVOX * rowb_fwd(CK) + 1023) / 1024 * 1024;
   const size_t smem = hbytes + (WLDS ? (size_t)NSTEP * MT * 1024 : 0);
-  auto kern = conv3d_bf16_fwd_kernel<CK, MT, WLDS>;
-  static SynOncePerDevice attr_done;
-  if (auto once_ = attr_done.first()) {
+  // the RELU instantiation: act 6 (the ReLU twin of act 5, run as its act 5) and act 3 (ReLU, alpha = 0) with statistics
+  const bool relu = a0.act == 6 || (a0.act == 3 && a0.stats_partial && a0.alpha == 0.f);
+  FwdArgs a = a0;
+  if (relu) a.act = 5;
+  auto kern = relu ? conv3d_bf16_fwd_kernel<CK, MT, WLDS, 0, true> : conv3d_bf16_fwd_kernel<CK, MT, WLDS>;
+  static SynOncePerDevice attr_done, attr_done_r;
+  if (auto once_ = (relu ? attr_done_r : attr_done).first()) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
   }
   hipLaunchKernelGGL(kern, dim3(gx, nchunks, a.ksplit), dim3(256), smem, st, a);
@@ -621,6 +636,7 @@ int launch_fwd(const FwdArgs& a, int nchunks, hipStream_t st, int* wgs_out) {
 }
 
 // split-K epilogue: fp32 partial sums [n4 x 4] -> + bias, activation, bf16
+template <bool RELU>
 __global__ void bf16_epilogue_kernel(const float* __restrict__ partial, const float* __restrict__ bias,
                                      const bf16_t* __restrict__ below, bf16_t* __restrict__ out, int64_t n4, int C4,
                                      int act, int ksplit, float alpha) {
@@ -654,10 +670,10 @@ __global__ void bf16_epilogue_kernel(const float* __restrict__ partial, const fl
       v[3] *= bf2f(b.y >> 16) > 0.f ? 1.f : alpha;
     } else if (act == 5) {
       const u32x2 b = *reinterpret_cast<const u32x2*>(below + i * 4);
-      v[0] = elu_f(v[0] + bf2f(b.x & 0xffffu));
-      v[1] = elu_f(v[1] + bf2f(b.x >> 16));
-      v[2] = elu_f(v[2] + bf2f(b.y & 0xffffu));
-      v[3] = elu_f(v[3] + bf2f(b.y >> 16));
+      v[0] = act5_f<RELU>(v[0] + bf2f(b.x & 0xffffu));
+      v[1] = act5_f<RELU>(v[1] + bf2f(b.x >> 16));
+      v[2] = act5_f<RELU>(v[2] + bf2f(b.y & 0xffffu));
+      v[3] = act5_f<RELU>(v[3] + bf2f(b.y >> 16));
     }
     u32x2 o;
     o.x = pack2(v[0], v[1]);
@@ -1068,8 +1084,8 @@ int synthsr_conv3d_bf16_pack_all(const float* params, void* packed, const int64_
 int synthsr_conv3d_bf16_fwd_ex(const void* in, const void* wp, const float* bias, void* out, const int shape[3], int Cin,
                                int Cout, int act, float alpha, const void* below, float* stats, float* scratch,
                                int64_t scratch_floats, synthsr_stream_t stream) {
-  if (!in || !wp || !out || !shape || Cin % 8 != 0 || Cout % 4 != 0 || act < 0 || act > 5 ||
-      ((act == 2 || act == 4 || act == 5) && !below) || (act == 5 && stats))
+  if (!in || !wp || !out || !shape || Cin % 8 != 0 || Cout % 4 != 0 || act < 0 || act > 6 ||
+      ((act == 2 || act == 4 || act >= 5) && !below) || (act >= 5 && stats))
     return SYNTHSR_EINVAL;
   const int64_t vox = (int64_t)shape[0] * shape[1] * shape[2];
   if (vox * Cin * 2 >= (1ll << 31) || vox * Cout * 2 >= (1ll << 31)) return SYNTHSR_EINVAL;
@@ -1124,8 +1140,9 @@ int synthsr_conv3d_bf16_fwd_ex(const void* in, const void* wp, const float* bias
   if (rc != SYNTHSR_OK) return rc;
   if (a.partial) {
     const int64_t n4 = vox * (Cout / 4);
-    hipLaunchKernelGGL(bf16_epilogue_kernel, dim3(syn_grid(n4, 256)), dim3(256), 0, st, scratch, bias, (const bf16_t*)below,
-                       (bf16_t*)out, n4, Cout / 4, act, a.ksplit, a.alpha);
+    hipLaunchKernelGGL((act == 6 ? bf16_epilogue_kernel<true> : bf16_epilogue_kernel<false>), dim3(syn_grid(n4, 256)), dim3(256),
+                       0, st, scratch, bias, (const bf16_t*)below, (bf16_t*)out, n4, Cout / 4, act == 6 ? 5 : act, a.ksplit,
+                       a.alpha);
     if (hipGetLastError() != hipSuccess) return SYNTHSR_ELAUNCH;
     if (stats) {
       hipLaunchKernelGGL(bf16_small_stats_kernel, dim3(Cout), dim3(256), 0, st, (const bf16_t*)out, vox, Cout, stats);
@@ -1300,7 +1317,7 @@ int synthsr_conv3d_bf16_up_dgrad(const void* dout, const void* wpacked8, void* d
   if (rc != SYNTHSR_OK) return rc;
   if (a.partial) {
     const int64_t n4 = vox * (Cl / 4);
-    hipLaunchKernelGGL(bf16_epilogue_kernel, dim3(syn_grid(n4, 256)), dim3(256), 0, st, scratch, (const float*)nullptr,
+    hipLaunchKernelGGL(bf16_epilogue_kernel<false>, dim3(syn_grid(n4, 256)), dim3(256), 0, st, scratch, (const float*)nullptr,
                        (const bf16_t*)nullptr, (bf16_t*)dlo, n4, Cl / 4, 0, a.ksplit, 0.f);
     if (hipGetLastError() != hipSuccess) return SYNTHSR_ELAUNCH;
   }

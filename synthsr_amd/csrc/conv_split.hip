@@ -158,12 +158,23 @@ __device__ __forceinline__ float elu_f(float v) {
   return v > 0.f ? v : n;
 }
 __device__ __forceinline__ float elu_dy(float y) { return y > 0.f ? 1.f : y + 1.f; }
+// ReLU family (act 3 / 4, as conv3d.hip): a template parameter of the kernels, so the ELU instantiations stay as they were
+template <bool RELU>
+__device__ __forceinline__ float act_f(float v) {
+  if constexpr (RELU) return fmaxf(v, 0.f);
+  else return elu_f(v);
+}
+template <bool RELU>
+__device__ __forceinline__ float act_dy(float y) {
+  if constexpr (RELU) return y > 0.f ? 1.f : 0.f;
+  else return elu_dy(y);
+}
 
 struct SplitFwdArgs {
   const float* in;
   const u32x4* wp;      // [piece 3][co-chunk][cc][step 7][mt][lane 64] x 8 bf16
   const float* bias;
-  const float* addend;  // act 0 / 1: added before the activation (may be `out`); act 2: ELU output of the layer below
+  const float* addend;  // act 0 / 1 / 3: added before the activation (may be `out`); act 2 / 4: output of the layer below
   float* out;
   float* stats_partial;  // [gridDim.x][2 Cout] per-workgroup-column sums | sums of squares of the output (ST), or null
   int D0, D1, D2, Cin, Cout, ncc, tiles1, tiles2, ntiles, act;
@@ -175,7 +186,7 @@ struct SplitFwdArgs {
 // output parities are K chunks (chunk = parity * ncc + input-channel chunk): parity p stages the sub-lattice dz[2 v + p] and
 // multiplies by its transposed 8-tap set (2 K steps, taps syn_split_tap8), whose 2x2x2 window starts at halo offset 1 - p per
 // axis.  wp = 8 parity sets [piece][co-chunk][cc][step 2][mt][lane], back to back.
-template <int MT, bool ST, int UPM = 0, int NPROD = 6>
+template <int MT, bool ST, int UPM = 0, int NPROD = 6, bool RELU = false>
 __global__ __launch_bounds__(256, 2) void conv3d_split_fwd_kernel(const SplitFwdArgs a) {
   static_assert(NPROD == 6 || NPROD == 9, "six partial products, or all nine");
   static_assert(UPM == 0 || UPM == 2, "the folded forward pass has its own kernel");
@@ -443,11 +454,11 @@ __global__ __launch_bounds__(256, 2) void conv3d_split_fwd_kernel(const SplitFwd
           if constexpr (ADD || ACT == 2) {
             const f32x4 b = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(radd, (int)off, 0, 0));
 #pragma unroll
-            for (int i = 0; i < 4; ++i) v[i] = ACT == 2 ? v[i] * elu_dy(b[i]) : v[i] + b[i];
+            for (int i = 0; i < 4; ++i) v[i] = ACT == 2 ? v[i] * act_dy<RELU>(b[i]) : v[i] + b[i];
           }
           if constexpr (ACT == 1) {
 #pragma unroll
-            for (int i = 0; i < 4; ++i) v[i] = elu_f(v[i]);
+            for (int i = 0; i < 4; ++i) v[i] = act_f<RELU>(v[i]);
           }
           __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rout, (int)off, 0, 0);
           if constexpr (ST) {
@@ -518,7 +529,7 @@ __global__ __launch_bounds__(256, 2) void conv3d_split_fwd_kernel(const SplitFwd
 // tile's K loop was built too: two copies of the K loop behind an if / else cost ~100 spilled registers, and without that the
 // gain was nil -- profiles/r04_split_fwd2_ablation.txt: what is left is exposed memory latency and the instruction mix, not
 // phases.)  Activation / addend handling is a template parameter: EPI 0 linear, 1 ELU, 2 x ELU'(addend), 3 + addend,
-// 4 ELU(. + addend).
+// 4 ELU(. + addend); 5 / 6 / 7 are the ReLU twins of 1 / 2 / 4 (epi_base below).
 //
 // STK (round 4, the Cout = 24 layers: 160^3, the matrix pipe's largest customers): the three bf16 pieces of the weights are stacked
 // along M instead of padding 24 output channels to two 16-row tiles per piece.  The six products a0 b0 + a0 b1 + a1 b0 + a1 b1 +
@@ -538,13 +549,18 @@ constexpr int STK_TILES = 5;
 // with its own double-buffered image; at the end of a tile the halves exchange half of their accumulators through LDS (the image
 // buffer that was consumed last) and each runs the epilogue of two of the four y rows.  The serial chain of a workgroup halves
 // (24 -> 12 chunks at 192 input channels) without staging anything twice, and every SIMD holds two waves instead of one.
-template <int MT, bool ST, int EPI, bool STK, int KS = 1>
+// EPI 5 / 6 / 7 (ReLU, x ReLU'(addend), ReLU(. + addend)) run the code of EPI 1 / 2 / 4 with the ReLU functions
+constexpr int epi_base(int epi) { return epi == 5 ? 1 : (epi == 6 ? 2 : (epi == 7 ? 4 : epi)); }
+
+template <int MT, bool ST, int EPI0, bool STK, int KS = 1>
 __global__ __launch_bounds__(256 * KS, KS == 1 ? 2 : 1) void conv3d_split_fwd2_kernel(const SplitFwdArgs a) {
   static_assert(KS == 1 || (KS == 2 && !STK), "split-K halves: the plain layout");
   constexpr int NSTEP = NSTEP27;
   constexpr int TYE = TY / KS;              // y rows whose epilogue a wave runs (KS = 2: each half takes two of the four)
   constexpr int NITEM = TYE * MT;           // epilogue items: one f32x4 (4 channels of a voxel) per lane each
   constexpr int NWT = STK ? STK_TILES : MT; // weight row tiles per piece set (STK: of the stacked set) = accumulators per row
+  constexpr int EPI = epi_base(EPI0);
+  constexpr bool RELU = EPI0 >= 5;
   static_assert(!ST || EPI <= 1, "statistics belong to plain forward convs");
   static_assert(!STK || MT == 2, "the stacked layout is the 24-channel one (two output tiles)");
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
@@ -727,7 +743,7 @@ __global__ __launch_bounds__(256 * KS, KS == 1 ? 2 : 1) void conv3d_split_fwd2_k
     for (int i = 0; i < 4; ++i) v[i] += bj[i];
     if constexpr (EPI == 2) {
 #pragma unroll
-      for (int i = 0; i < 4; ++i) v[i] *= elu_dy(eb[j % ENB][i]);
+      for (int i = 0; i < 4; ++i) v[i] *= act_dy<RELU>(eb[j % ENB][i]);
     }
     if constexpr (EPI == 3 || EPI == 4) {
 #pragma unroll
@@ -735,7 +751,7 @@ __global__ __launch_bounds__(256 * KS, KS == 1 ? 2 : 1) void conv3d_split_fwd2_k
     }
     if constexpr (EPI == 1 || EPI == 4) {
 #pragma unroll
-      for (int i = 0; i < 4; ++i) v[i] = elu_f(v[i]);
+      for (int i = 0; i < 4; ++i) v[i] = act_f<RELU>(v[i]);
     }
     ev = v;
   };
@@ -1013,8 +1029,10 @@ struct F3Cfg {
   static constexpr int SMEM = 2 * BUF + (WDB ? 2 : 1) * WBYTES + MT * 64;
 };
 
-template <int MT, bool ST, int EPI>
+template <int MT, bool ST, int EPI0>
 __global__ __launch_bounds__(512, 1) void conv3d_split_fwd3_kernel(const SplitFwdArgs a) {
+  constexpr int EPI = epi_base(EPI0);
+  constexpr bool RELU = EPI0 >= 5;
   using C = F3Cfg<MT>;
   constexpr int NSTEP = NSTEP27, RW = 2, NTHR = 512;
   constexpr int NITEM = RW * MT;  // epilogue items per lane: one f32x4 (4 channels of a voxel) each
@@ -1177,7 +1195,7 @@ __global__ __launch_bounds__(512, 1) void conv3d_split_fwd3_kernel(const SplitFw
     for (int i = 0; i < 4; ++i) v[i] += bj[i];
     if constexpr (EPI == 2) {
 #pragma unroll
-      for (int i = 0; i < 4; ++i) v[i] *= elu_dy(eb[EPI >= 2 ? j : 0][i]);
+      for (int i = 0; i < 4; ++i) v[i] *= act_dy<RELU>(eb[EPI >= 2 ? j : 0][i]);
     }
     if constexpr (EPI == 3 || EPI == 4) {
 #pragma unroll
@@ -1185,7 +1203,7 @@ __global__ __launch_bounds__(512, 1) void conv3d_split_fwd3_kernel(const SplitFw
     }
     if constexpr (EPI == 1 || EPI == 4) {
 #pragma unroll
-      for (int i = 0; i < 4; ++i) v[i] = elu_f(v[i]);
+      for (int i = 0; i < 4; ++i) v[i] = act_f<RELU>(v[i]);
     }
     ev = v;
   };
@@ -1393,7 +1411,7 @@ __global__ __launch_bounds__(512, 1) void conv3d_split_fwd3_kernel(const SplitFw
 // 4x4x16 low-resolution tile, two x-rows per wave; accumulators for NPAR parities x 2 rows x MT co-tiles stay in registers over
 // the input-channel chunks (register budget: NPAR = 4, or 2 for MT = 3; blockIdx.z = parity group).  Per chunk 2 NPAR K steps (parity, step) of
 // 6 x 2 x MT MFMAs, weights one step ahead (two register sets), activations re-loaded per step.  D0..D2 = the low-res grid.
-template <int MT, int NPAR, int NPROD = 6>
+template <int MT, int NPAR, int NPROD = 6, bool RELU = false>
 __global__ __launch_bounds__(512, 1) void conv3d_split_upfwd_kernel(const SplitFwdArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
   // Round 6 (second half): wave = (parity q of the group, part of the tile) instead of (z plane, y half) x all parities: a wave
@@ -1556,7 +1574,7 @@ __global__ __launch_bounds__(512, 1) void conv3d_split_upfwd_kernel(const SplitF
         }
         if (a.act == 1) {
 #pragma unroll
-          for (int i = 0; i < 4; ++i) v[i] = elu_f(v[i]);
+          for (int i = 0; i < 4; ++i) v[i] = act_f<RELU>(v[i]);
         }
         __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rout, (int)off, 0, 0);
       }
@@ -1584,14 +1602,24 @@ inline int split_grid_x(int ntiles, int nchunks) {
   return gx;
 }
 
+// act 3 / 4 (ReLU family): the RELU instantiation of the generic kernels under the ELU family's codes 1 / 2
+inline bool relu_args(const SplitFwdArgs& a, SplitFwdArgs& b) {
+  b = a;
+  if (a.act < 3) return false;
+  b.act -= 2;
+  return true;
+}
+
 template <int MT, int NPAR, int NPROD>
-int launch_split_upfwd_np(const SplitFwdArgs& a, hipStream_t st) {
+int launch_split_upfwd_np(const SplitFwdArgs& a0, hipStream_t st) {
   constexpr int NG = 8 / NPAR;
+  SplitFwdArgs a;
+  const bool relu = relu_args(a0, a);
   const int gx = split_upfwd_grid_x(a.ntiles, NG);
   const size_t smem = 2 * BUF;
-  auto kern = conv3d_split_upfwd_kernel<MT, NPAR, NPROD>;
-  static SynOncePerDevice attr_done;
-  if (auto once_ = attr_done.first()) {
+  auto kern = relu ? conv3d_split_upfwd_kernel<MT, NPAR, NPROD, true> : conv3d_split_upfwd_kernel<MT, NPAR, NPROD>;
+  static SynOncePerDevice attr_done, attr_done_r;
+  if (auto once_ = (relu ? attr_done_r : attr_done).first()) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
   }
   hipLaunchKernelGGL(kern, dim3(gx, 1, NG), dim3(512), smem, st, a);
@@ -1604,11 +1632,13 @@ int launch_split_upfwd(const SplitFwdArgs& a, hipStream_t st) {
 }
 
 template <int MT, bool ST, int UPM, int NPROD>
-int launch_split_fwd_np(const SplitFwdArgs& a, int gx, int nchunks, hipStream_t st) {
+int launch_split_fwd_np(const SplitFwdArgs& a0, int gx, int nchunks, hipStream_t st) {
+  SplitFwdArgs a;
+  const bool relu = relu_args(a0, a);
   const size_t smem = 2 * BUF;
-  auto kern = conv3d_split_fwd_kernel<MT, ST, UPM, NPROD>;
-  static SynOncePerDevice attr_done;
-  if (auto once_ = attr_done.first()) {
+  auto kern = relu ? conv3d_split_fwd_kernel<MT, ST, UPM, NPROD, true> : conv3d_split_fwd_kernel<MT, ST, UPM, NPROD>;
+  static SynOncePerDevice attr_done, attr_done_r;
+  if (auto once_ = (relu ? attr_done_r : attr_done).first()) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
   }
   hipLaunchKernelGGL(kern, dim3(gx, nchunks), dim3(256), smem, st, a);
@@ -1645,10 +1675,18 @@ int launch_split_fwd2_e(const SplitFwdArgs& a, int gx, int nchunks, hipStream_t 
   return hipGetLastError() == hipSuccess ? SYNTHSR_OK : SYNTHSR_ELAUNCH;
 }
 
+// EPI of the fwd2 / fwd3 kernels for act 0-4 with or without an addend
+inline int split_epi(const SplitFwdArgs& a) {
+  if (a.act == 3) return a.addend ? 7 : 5;
+  if (a.act == 4) return 6;
+  return a.act + ((a.addend && a.act < 2) ? 3 : 0);
+}
+
 template <int MT, bool ST, bool STK = false>
 int launch_split_fwd2(const SplitFwdArgs& a, int gx, int nchunks, hipStream_t st) {
-  const int epi = a.act + ((a.addend && a.act < 2) ? 3 : 0);
+  const int epi = split_epi(a);
   if constexpr (ST) {
+    if (epi == 5) return launch_split_fwd2_e<MT, true, 5, STK>(a, gx, nchunks, st);
     return epi == 1 ? launch_split_fwd2_e<MT, true, 1, STK>(a, gx, nchunks, st) : launch_split_fwd2_e<MT, true, 0, STK>(a, gx, nchunks, st);
   } else {
     switch (epi) {
@@ -1656,6 +1694,9 @@ int launch_split_fwd2(const SplitFwdArgs& a, int gx, int nchunks, hipStream_t st
       case 1: return launch_split_fwd2_e<MT, false, 1, STK>(a, gx, nchunks, st);
       case 2: return launch_split_fwd2_e<MT, false, 2, STK>(a, gx, nchunks, st);
       case 3: return launch_split_fwd2_e<MT, false, 3, STK>(a, gx, nchunks, st);
+      case 5: return launch_split_fwd2_e<MT, false, 5, STK>(a, gx, nchunks, st);
+      case 6: return launch_split_fwd2_e<MT, false, 6, STK>(a, gx, nchunks, st);
+      case 7: return launch_split_fwd2_e<MT, false, 7, STK>(a, gx, nchunks, st);
       default: return launch_split_fwd2_e<MT, false, 4, STK>(a, gx, nchunks, st);
     }
   }
@@ -1689,8 +1730,9 @@ int launch_split_fwd3_e(const SplitFwdArgs& a, int nchunks, hipStream_t st) {
 
 template <int MT, bool ST>
 int launch_split_fwd3(const SplitFwdArgs& a, int nchunks, hipStream_t st) {
-  const int epi = a.act + ((a.addend && a.act < 2) ? 3 : 0);
+  const int epi = split_epi(a);
   if constexpr (ST) {
+    if (epi == 5) return launch_split_fwd3_e<MT, true, 5>(a, nchunks, st);
     return epi == 1 ? launch_split_fwd3_e<MT, true, 1>(a, nchunks, st) : launch_split_fwd3_e<MT, true, 0>(a, nchunks, st);
   } else {
     switch (epi) {
@@ -1698,6 +1740,9 @@ int launch_split_fwd3(const SplitFwdArgs& a, int nchunks, hipStream_t st) {
       case 1: return launch_split_fwd3_e<MT, false, 1>(a, nchunks, st);
       case 2: return launch_split_fwd3_e<MT, false, 2>(a, nchunks, st);
       case 3: return launch_split_fwd3_e<MT, false, 3>(a, nchunks, st);
+      case 5: return launch_split_fwd3_e<MT, false, 5>(a, nchunks, st);
+      case 6: return launch_split_fwd3_e<MT, false, 6>(a, nchunks, st);
+      case 7: return launch_split_fwd3_e<MT, false, 7>(a, nchunks, st);
       default: return launch_split_fwd3_e<MT, false, 4>(a, nchunks, st);
     }
   }
@@ -2497,7 +2542,7 @@ extern "C" __attribute__((visibility("hidden"))) int syn_split_fwd(const float* 
   t_nprod = nprod;
   if ((Cin % 8) != 0 || (Cout % 4) != 0 || mt < 1 || mt > 3 || nchunks < 1 || (upm != 0 && upm != 2)) return SYNTHSR_EINVAL;
   if (stacked && (Cout != 24 || mt != 2 || nchunks != 1 || upm != 0 || t_nprod != 6)) return SYNTHSR_EINVAL;
-  if (stats && (!partial || addend || act == 2 || upm)) return SYNTHSR_EINVAL;
+  if (act < 0 || act > 4 || (stats && (!partial || addend || act == 2 || act == 4 || upm))) return SYNTHSR_EINVAL;
   if (upm && (bias || addend || act != 0)) return SYNTHSR_EINVAL;
   const int64_t vox = (int64_t)s[0] * s[1] * s[2];
   if ((upm ? 8 : 1) * vox * Cin * 4 >= (1ll << 31) || vox * Cout * 4 >= (1ll << 31)) return SYNTHSR_EINVAL;
@@ -2533,13 +2578,13 @@ extern "C" __attribute__((visibility("hidden"))) int syn_split_fwd(const float* 
 }
 
 // forward pass of the up-sampled channel range of a folded decoder conv: lo [s][Cin] -> out [2 s][Cout] (Cout <= 48: one co-chunk),
-// wp = 8 parity sets in the split layout; act 0 / 1, optional bias and addend (indexed like the output)
+// wp = 8 parity sets in the split layout; act 0 / 1 / 3, optional bias and addend (indexed like the output)
 extern "C" __attribute__((visibility("hidden"))) int syn_split_upfwd(const float* lo, const float* wp, const float* bias,
                                                                       const float* addend, float* out, const int s[3], int Cin,
                                                                       int Cout, int mt, int act, int nprod, hipStream_t st) {
   if (nprod != 6 && nprod != 9) return SYNTHSR_EINVAL;
   t_nprod = nprod;
-  if ((Cin % 8) != 0 || (Cout % 4) != 0 || mt < 1 || mt > 3 || Cout > 16 * mt || (act != 0 && act != 1)) return SYNTHSR_EINVAL;
+  if ((Cin % 8) != 0 || (Cout % 4) != 0 || mt < 1 || mt > 3 || Cout > 16 * mt || (act != 0 && act != 1 && act != 3)) return SYNTHSR_EINVAL;
   const int64_t vox = (int64_t)s[0] * s[1] * s[2];
   if (vox * Cin * 4 >= (1ll << 31) || 8 * vox * Cout * 4 >= (1ll << 31)) return SYNTHSR_EINVAL;
   SplitFwdArgs a;

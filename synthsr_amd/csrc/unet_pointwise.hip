@@ -26,6 +26,13 @@ struct Shape3 {
 };
 
 __device__ __forceinline__ float elu_grad_from_y(float y) { return y > 0.f ? 1.f : y + 1.f; }  // alpha = 1
+// activation derivative through the output y: ELU (act 1) or, for the RELU instantiations (act 3), ReLU'(y) = 1 for y > 0
+// else 0 (TF ReluGrad); a template parameter so that the ELU kernels stay the code they were
+template <bool RELU>
+__device__ __forceinline__ float act_grad_from_y(float y) {
+  if constexpr (RELU) return y > 0.f ? 1.f : 0.f;
+  else return elu_grad_from_y(y);
+}
 
 __device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
 __device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
@@ -109,7 +116,7 @@ __device__ __forceinline__ void block_scalar_add(float v, float* slot) {
 // dz = (dy [+ dy2]) * elu'(y); dbias[c] += sum dz
 // Optional fused BatchNorm backward (bn_sums != nullptr): the incoming gradient is w.r.t. the BN OUTPUT of y and is
 // first mapped to the BN input, g <- gamma*invstd*(g - sum_dy/n - xhat*sum_dyxhat/n), saving one full pass.
-template <typename T>
+template <typename T, bool RELU = false>
 __global__ __launch_bounds__(RB) void elu_bwd_kernel(const T* __restrict__ dy, const T* __restrict__ dy2,
                                                      const T* __restrict__ y, T* __restrict__ dz,
                                                      float* __restrict__ dbias, int64_t n4, int C4,
@@ -161,10 +168,10 @@ __global__ __launch_bounds__(RB) void elu_bwd_kernel(const T* __restrict__ dy, c
       g.x += g2.x; g.y += g2.y; g.z += g2.z; g.w += g2.w;
     }
     float4 r;
-    r.x = g.x * elu_grad_from_y(a.x);
-    r.y = g.y * elu_grad_from_y(a.y);
-    r.z = g.z * elu_grad_from_y(a.z);
-    r.w = g.w * elu_grad_from_y(a.w);
+    r.x = g.x * act_grad_from_y<RELU>(a.x);
+    r.y = g.y * act_grad_from_y<RELU>(a.y);
+    r.z = g.z * act_grad_from_y<RELU>(a.z);
+    r.w = g.w * act_grad_from_y<RELU>(a.w);
     st4(dz + i * 4, r);
     if (dbias) {
       if (fixed) {
@@ -425,7 +432,7 @@ __global__ __launch_bounds__(RB) void bn_maxpool_bwd_sums_kernel(const T* __rest
 // raster order of y * sc + sh), applies g <- gamma * invstd * (g - sum_dy / n - xhat * sum_dyxhat / n) to all 8 voxels
 // (sums from bn_maxpool_bwd_sums_kernel with dbn = nullptr), adds the skip connection's gradient dy2 and multiplies by
 // ELU'(y); dbias += sum dz.
-template <typename T>
+template <typename T, bool RELU = false>
 __global__ __launch_bounds__(RB) void bn_pool_elu_bwd_kernel(const T* __restrict__ dpool, const T* __restrict__ y,
                                                              const T* __restrict__ dy2, T* __restrict__ dz,
                                                              float* __restrict__ dbias, Shape3 s, int C,
@@ -489,10 +496,10 @@ __global__ __launch_bounds__(RB) void bn_pool_elu_bwd_kernel(const T* __restrict
         gg[0] += g2.x; gg[1] += g2.y; gg[2] += g2.z; gg[3] += g2.w;
       }
       float4 o;
-      o.x = gg[0] * elu_grad_from_y(aa[0]);
-      o.y = gg[1] * elu_grad_from_y(aa[1]);
-      o.z = gg[2] * elu_grad_from_y(aa[2]);
-      o.w = gg[3] * elu_grad_from_y(aa[3]);
+      o.x = gg[0] * act_grad_from_y<RELU>(aa[0]);
+      o.y = gg[1] * act_grad_from_y<RELU>(aa[1]);
+      o.z = gg[2] * act_grad_from_y<RELU>(aa[2]);
+      o.w = gg[3] * act_grad_from_y<RELU>(aa[3]);
       st4(dz + vi * C + c, o);
       if (dbias) {
         if (fixed) {
@@ -1160,35 +1167,39 @@ inline bool odd_shape(const int s[3]) { return (s[0] | s[1] | s[2]) & 1; }
 }  // namespace
 
 // ---- entry-point bodies, templated on the activation type (float | bf16_t)
+// activation codes of the backward entry points: 1 ELU, 3 ReLU (the forward codes of synthsr_conv3d_fwd)
+inline bool ok_act(int act) { return act == 1 || act == 3; }
+
 template <typename T>
-int elu_bwd_t(const T* dy, const T* dy2, const T* y, T* dz, float* dbias, int64_t nvox, int C, synthsr_stream_t stream) {
-  if (!dy || !y || !dz || nvox < 1 || !ok_c4(C)) return SYNTHSR_EINVAL;
+int elu_bwd_t(const T* dy, const T* dy2, const T* y, T* dz, float* dbias, int64_t nvox, int C, synthsr_stream_t stream,
+              int act = 1) {
+  if (!dy || !y || !dz || nvox < 1 || !ok_c4(C) || !ok_act(act)) return SYNTHSR_EINVAL;
   const int64_t n4 = nvox * (C / 4);
-  hipLaunchKernelGGL(elu_bwd_kernel<T>, dim3(syn_grid(n4, RB, red_grid())), dim3(RB), C * sizeof(float), (hipStream_t)stream, dy,
+  hipLaunchKernelGGL((act == 3 ? elu_bwd_kernel<T, true> : elu_bwd_kernel<T>), dim3(syn_grid(n4, RB, red_grid())), dim3(RB), C * sizeof(float), (hipStream_t)stream, dy,
                      dy2, y, dz, dbias, n4, C / 4, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr,
-                     0.f, 0.f, (const float*)nullptr, (const float*)nullptr);
+                     0.f, 0.f, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, (int64_t)0);
   SYN_CHECK_LAUNCH();
   return SYNTHSR_OK;
 }
 
 template <typename T>
-int bn_elu_bwd_t(const T* dy, const T* dy2, const T* y, T* dz, float* dbias, int64_t nvox, int C, const float* stats, const float* gamma, float eps, const float* sums, synthsr_stream_t stream) {
-  if (!dy || !y || !dz || !stats || !gamma || !sums || nvox < 1 || !ok_c4(C)) return SYNTHSR_EINVAL;
+int bn_elu_bwd_t(const T* dy, const T* dy2, const T* y, T* dz, float* dbias, int64_t nvox, int C, const float* stats, const float* gamma, float eps, const float* sums, synthsr_stream_t stream, int act = 1) {
+  if (!dy || !y || !dz || !stats || !gamma || !sums || nvox < 1 || !ok_c4(C) || !ok_act(act)) return SYNTHSR_EINVAL;
   const int64_t n4 = nvox * (C / 4);
-  hipLaunchKernelGGL(elu_bwd_kernel<T>, dim3(syn_grid(n4, RB, red_grid())), dim3(RB), C * sizeof(float), (hipStream_t)stream, dy,
+  hipLaunchKernelGGL((act == 3 ? elu_bwd_kernel<T, true> : elu_bwd_kernel<T>), dim3(syn_grid(n4, RB, red_grid())), dim3(RB), C * sizeof(float), (hipStream_t)stream, dy,
                      dy2, y, dz, dbias, n4, C / 4, stats, gamma, sums, eps, (float)(1.0 / (double)nvox),
-                     (const float*)nullptr, (const float*)nullptr);
+                     (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, (int64_t)0);
   SYN_CHECK_LAUNCH();
   return SYNTHSR_OK;
 }
 
 template <typename T>
-int bn_elu_bwd_head_t(const float* dpred, const float* whead, const T* y, T* dz, float* dbias, int64_t nvox, int C, const float* stats, const float* gamma, float eps, const float* sums, synthsr_stream_t stream) {
-  if (!dpred || !whead || !y || !dz || !stats || !gamma || !sums || nvox < 1 || !ok_c4(C)) return SYNTHSR_EINVAL;
+int bn_elu_bwd_head_t(const float* dpred, const float* whead, const T* y, T* dz, float* dbias, int64_t nvox, int C, const float* stats, const float* gamma, float eps, const float* sums, synthsr_stream_t stream, int act = 1) {
+  if (!dpred || !whead || !y || !dz || !stats || !gamma || !sums || nvox < 1 || !ok_c4(C) || !ok_act(act)) return SYNTHSR_EINVAL;
   const int64_t n4 = nvox * (C / 4);
-  hipLaunchKernelGGL(elu_bwd_kernel<T>, dim3(syn_grid(n4, RB, red_grid())), dim3(RB), C * sizeof(float), (hipStream_t)stream,
+  hipLaunchKernelGGL((act == 3 ? elu_bwd_kernel<T, true> : elu_bwd_kernel<T>), dim3(syn_grid(n4, RB, red_grid())), dim3(RB), C * sizeof(float), (hipStream_t)stream,
                      (const T*)nullptr, (const T*)nullptr, y, dz, dbias, n4, C / 4, stats, gamma, sums, eps,
-                     (float)(1.0 / (double)nvox), dpred, whead);
+                     (float)(1.0 / (double)nvox), dpred, whead, (const float*)nullptr, (int64_t)0);
   SYN_CHECK_LAUNCH();
   return SYNTHSR_OK;
 }
@@ -1246,13 +1257,14 @@ int bn_maxpool_bwd_ex_t(const T* dy, const T* x, T* dbn, const int shape[3], int
 template <typename T>
 int bn_pool_elu_bwd_t(const T* dpool, const T* y, const T* dy2, T* dz, float* dbias, const int shape[3], int C,
                       const float* stats, const float* gamma, const float* beta, const float* sums, float eps,
-                      synthsr_stream_t stream) {
-  if (!dpool || !y || !dz || !stats || !gamma || !beta || !sums || bad_shape(shape) || odd_shape(shape) || !ok_c4(C))
+                      synthsr_stream_t stream, int act = 1) {
+  if (!dpool || !y || !dz || !stats || !gamma || !beta || !sums || bad_shape(shape) || odd_shape(shape) || !ok_c4(C) ||
+      !ok_act(act))
     return SYNTHSR_EINVAL;
   Shape3 s{{shape[0], shape[1], shape[2]}};
   const int64_t n4 = (int64_t)(s.d[0] / 2) * (s.d[1] / 2) * (s.d[2] / 2) * (C / 4);
   const float inv_n = 1.0f / (float)((int64_t)s.d[0] * s.d[1] * s.d[2]);
-  hipLaunchKernelGGL(bn_pool_elu_bwd_kernel<T>, dim3(syn_grid(n4, RB, red_grid())), dim3(RB), C * sizeof(float),
+  hipLaunchKernelGGL((act == 3 ? bn_pool_elu_bwd_kernel<T, true> : bn_pool_elu_bwd_kernel<T>), dim3(syn_grid(n4, RB, red_grid())), dim3(RB), C * sizeof(float),
                      (hipStream_t)stream, dpool, y, dy2, dz, dbias, s, C, stats, gamma, beta, sums, eps, inv_n);
   SYN_CHECK_LAUNCH();
   return SYNTHSR_OK;
@@ -1398,14 +1410,14 @@ int head_bwd_t(const float* dpred, const T* x, int64_t nvox, int C, const float*
 template <typename T>
 static int elu_bwd_drop_t(const T* dy, const T* dy2, const T* y, T* dz, float* dbias, int64_t nvox, int C, const float* stats,
                           const float* gamma, float eps, const float* sums, const float* dpred, const float* whead,
-                          const float* drop, int64_t nvox_per_sample, synthsr_stream_t stream) {
+                          const float* drop, int64_t nvox_per_sample, synthsr_stream_t stream, int act = 1) {
   const bool bn = stats || gamma || sums, head = dpred || whead;
-  if (!y || !dz || !drop || nvox < 1 || !ok_c4(C) || nvox_per_sample < 1 || (nvox % nvox_per_sample) != 0 ||
+  if (!y || !dz || !drop || nvox < 1 || !ok_c4(C) || !ok_act(act) || nvox_per_sample < 1 || (nvox % nvox_per_sample) != 0 ||
       (bn && (!stats || !gamma || !sums)) || (head && (!dpred || !whead || !bn || dy || dy2)) || (!head && !dy))
     return SYNTHSR_EINVAL;
   const int64_t n4 = nvox * (C / 4);
-  hipLaunchKernelGGL(elu_bwd_kernel<T>, dim3(syn_grid(n4, RB, red_grid())), dim3(RB), C * sizeof(float), (hipStream_t)stream,
-                     dy, dy2, y, dz, dbias, n4, C / 4, stats, gamma, sums, eps, bn ? (float)(1.0 / (double)nvox) : 0.f, dpred,
+  hipLaunchKernelGGL((act == 3 ? elu_bwd_kernel<T, true> : elu_bwd_kernel<T>), dim3(syn_grid(n4, RB, red_grid())), dim3(RB),
+                     C * sizeof(float), (hipStream_t)stream, dy, dy2, y, dz, dbias, n4, C / 4, stats, gamma, sums, eps, bn ? (float)(1.0 / (double)nvox) : 0.f, dpred,
                      whead, drop, nvox_per_sample * (C / 4));
   SYN_CHECK_LAUNCH();
   return SYNTHSR_OK;
@@ -1463,6 +1475,60 @@ int synthsr_elu_bwd_drop_bf16(const void* dy, const void* dy2, const void* y, vo
                               const float* whead, const float* drop, int64_t nvox_per_sample, synthsr_stream_t stream) {
   return elu_bwd_drop_t<bf16_t>((const bf16_t*)dy, (const bf16_t*)dy2, (const bf16_t*)y, (bf16_t*)dz, dbias, nvox, C, stats, gamma,
                                 eps, sums, dpred, whead, drop, nvox_per_sample, stream);
+}
+
+// activation-generic twins of the five ELU-backward families (act 1 ELU, 3 ReLU; anything else SYNTHSR_EINVAL)
+int synthsr_act_bwd(const float* dy, const float* dy2, const float* y, float* dz, float* dbias, int64_t nvox, int C, int act,
+                    synthsr_stream_t stream) {
+  return elu_bwd_t<float>(dy, dy2, y, dz, dbias, nvox, C, stream, act);
+}
+int synthsr_act_bwd_bf16(const void* dy, const void* dy2, const void* y, void* dz, float* dbias, int64_t nvox, int C, int act,
+                         synthsr_stream_t stream) {
+  return elu_bwd_t<bf16_t>((const bf16_t*)dy, (const bf16_t*)dy2, (const bf16_t*)y, (bf16_t*)dz, dbias, nvox, C, stream, act);
+}
+int synthsr_bn_act_bwd(const float* dy, const float* dy2, const float* y, float* dz, float* dbias, int64_t nvox, int C,
+                       const float* stats, const float* gamma, float eps, const float* sums, int act, synthsr_stream_t stream) {
+  return bn_elu_bwd_t<float>(dy, dy2, y, dz, dbias, nvox, C, stats, gamma, eps, sums, stream, act);
+}
+int synthsr_bn_act_bwd_bf16(const void* dy, const void* dy2, const void* y, void* dz, float* dbias, int64_t nvox, int C,
+                            const float* stats, const float* gamma, float eps, const float* sums, int act,
+                            synthsr_stream_t stream) {
+  return bn_elu_bwd_t<bf16_t>((const bf16_t*)dy, (const bf16_t*)dy2, (const bf16_t*)y, (bf16_t*)dz, dbias, nvox, C, stats, gamma,
+                              eps, sums, stream, act);
+}
+int synthsr_bn_act_bwd_head(const float* dpred, const float* whead, const float* y, float* dz, float* dbias, int64_t nvox,
+                            int C, const float* stats, const float* gamma, float eps, const float* sums, int act,
+                            synthsr_stream_t stream) {
+  return bn_elu_bwd_head_t<float>(dpred, whead, y, dz, dbias, nvox, C, stats, gamma, eps, sums, stream, act);
+}
+int synthsr_bn_act_bwd_head_bf16(const float* dpred, const float* whead, const void* y, void* dz, float* dbias, int64_t nvox,
+                                 int C, const float* stats, const float* gamma, float eps, const float* sums, int act,
+                                 synthsr_stream_t stream) {
+  return bn_elu_bwd_head_t<bf16_t>(dpred, whead, (const bf16_t*)y, (bf16_t*)dz, dbias, nvox, C, stats, gamma, eps, sums, stream,
+                                   act);
+}
+int synthsr_act_bwd_drop(const float* dy, const float* dy2, const float* y, float* dz, float* dbias, int64_t nvox, int C,
+                         const float* stats, const float* gamma, float eps, const float* sums, const float* dpred,
+                         const float* whead, const float* drop, int64_t nvox_per_sample, int act, synthsr_stream_t stream) {
+  return elu_bwd_drop_t<float>(dy, dy2, y, dz, dbias, nvox, C, stats, gamma, eps, sums, dpred, whead, drop, nvox_per_sample, stream,
+                               act);
+}
+int synthsr_act_bwd_drop_bf16(const void* dy, const void* dy2, const void* y, void* dz, float* dbias, int64_t nvox, int C,
+                              const float* stats, const float* gamma, float eps, const float* sums, const float* dpred,
+                              const float* whead, const float* drop, int64_t nvox_per_sample, int act, synthsr_stream_t stream) {
+  return elu_bwd_drop_t<bf16_t>((const bf16_t*)dy, (const bf16_t*)dy2, (const bf16_t*)y, (bf16_t*)dz, dbias, nvox, C, stats, gamma,
+                                eps, sums, dpred, whead, drop, nvox_per_sample, stream, act);
+}
+int synthsr_bn_pool_act_bwd(const float* dpool, const float* y, const float* dy2, float* dz, float* dbias, const int shape[3],
+                            int C, const float* stats, const float* gamma, const float* beta, const float* sums, float eps,
+                            int act, synthsr_stream_t stream) {
+  return bn_pool_elu_bwd_t<float>(dpool, y, dy2, dz, dbias, shape, C, stats, gamma, beta, sums, eps, stream, act);
+}
+int synthsr_bn_pool_act_bwd_bf16(const void* dpool, const void* y, const void* dy2, void* dz, float* dbias, const int shape[3],
+                                 int C, const float* stats, const float* gamma, const float* beta, const float* sums, float eps,
+                                 int act, synthsr_stream_t stream) {
+  return bn_pool_elu_bwd_t<bf16_t>((const bf16_t*)dpool, (const bf16_t*)y, (const bf16_t*)dy2, (bf16_t*)dz, dbias, shape, C, stats,
+                                   gamma, beta, sums, eps, stream, act);
 }
 
 int synthsr_bn_stats(const float* x, int64_t nvox, int C, float* stats, double* ws, synthsr_stream_t stream) {

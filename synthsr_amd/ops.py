@@ -396,7 +396,7 @@ def conv3d_wgrad_part(x, dout, dw, ci_off, dbias=None):
 
 
 def conv3d(x, wpacked, bias, Cout, act=1, out=None):
-    """x [d0,d1,d2,Cin] -> [d0,d1,d2,Cout]; act: 0 linear, 1 ELU"""
+    """x [d0,d1,d2,Cin] -> [d0,d1,d2,Cout]; act: 0 linear, 1 ELU, 3 ReLU (bf16: the same codes, ReLU = act 3 at alpha 0)"""
     if x.dtype == torch.bfloat16:
         return conv3d_bf16(x, wpacked, bias, Cout, act, out=out)
     lib = _L()
@@ -425,17 +425,19 @@ def conv3d_stats(x, wpacked, bias, Cout, stats, ws, act=1, out=None):
 
 
 def conv3d_add(x, wpacked, bias, addend, Cout, act=1, out=None):
-    """act 0/1: act(conv3(x) + addend + bias), `addend` may be `out` itself (in-place accumulation);
-    act 2: conv3(x) * elu'(addend) -- data gradient fused with the ELU backward of the layer that produced `addend`"""
+    """act 0/1/3: act(conv3(x) + addend + bias), `addend` may be `out` itself (in-place accumulation);
+    act 2 / 4: conv3(x) * elu'(addend) / relu'(addend) -- data gradient fused with the ELU / ReLU backward of the layer that
+    produced `addend`"""
     if x.dtype == torch.bfloat16:
         if act == 0:
-            raise NotImplementedError('bf16: addend epilogues are ELU(conv + bias + addend) (act 1) and conv * ELU\'(addend) (act 2)')
-        return conv3d_bf16(x, wpacked, bias, Cout, 5 if act == 1 else 2, below=addend, out=out)
+            raise NotImplementedError('bf16: addend epilogues are act(conv + bias + addend) (act 1 / 3) and conv * act\'(addend) '
+                                      '(act 2 / 4)')
+        return conv3d_bf16(x, wpacked, bias, Cout, {1: 5, 2: 2, 3: 6, 4: 4}[act], below=addend, out=out)
     lib = _L()
     s = x.shape
     if out is None:
         out = torch.empty((s[0], s[1], s[2], Cout), dtype=torch.float32, device=x.device)
-    with _Timed('conv3d_dgrad' if act == 2 else 'conv3d_fwd', s[:3], s[3], Cout):
+    with _Timed('conv3d_dgrad' if act in (2, 4) else 'conv3d_fwd', s[:3], s[3], Cout):
         _lib.check(lib.synthsr_conv3d_fwd_add(conv_ctx(), _lib.ptr(x), _lib.ptr(wpacked), _lib.ptr(bias), _lib.ptr(addend),
                                               _lib.ptr(out), _lib.i3(s[:3]), int(s[3]), int(Cout), int(act),
                                               _lib.stream()), 'conv3d_fwd_add')
@@ -449,14 +451,14 @@ def conv3d_wgrad(x, dout, dw, dbias=None):
     return conv3d_wgrad_part(x, dout, dw, 0, dbias)
 
 
-def elu_bwd(dy, y, dy2=None, dbias=None, out=None):
-    lib = _L()
+def elu_bwd(dy, y, dy2=None, dbias=None, out=None, act=1):
+    """dz = (dy + dy2) * act'(y) (act 1 ELU, 3 ReLU: y the stored activation output); dbias += sum dz"""
     C = int(y.shape[-1])
     nvox = y.numel() // C
     if out is None:
         out = torch.empty_like(y)
-    _lib.check(_sym('synthsr_elu_bwd', y)(_lib.ptr(dy), _lib.ptr(dy2), _lib.ptr(y), _lib.ptr(out), _lib.ptr(dbias), nvox, C,
-                                   _lib.stream()), 'elu_bwd')
+    _lib.check(_sym('synthsr_act_bwd', y)(_lib.ptr(dy), _lib.ptr(dy2), _lib.ptr(y), _lib.ptr(out), _lib.ptr(dbias), nvox, C,
+                                          int(act), _lib.stream()), 'act_bwd')
     return out
 
 
@@ -477,7 +479,7 @@ def scale_channels(x, scale, out=None):
     return out
 
 
-def elu_bwd_drop(dy, y, drop, dy2=None, dbias=None, out=None, bn=None, head=None, eps=BN_EPS):
+def elu_bwd_drop(dy, y, drop, dy2=None, dbias=None, out=None, bn=None, head=None, eps=BN_EPS, act=1):
     """ELU backward of a conv output y ([B * d0, d1, d2, C]) whose consumer read drop[b, c] * y (see synthsr_elu_bwd_drop);
     bn = (stats, gamma, sums) when that consumer is a BatchNorm, head = (dpred, whead) for the rank-1 gradient of the head"""
     C = int(y.shape[-1])
@@ -487,9 +489,10 @@ def elu_bwd_drop(dy, y, drop, dy2=None, dbias=None, out=None, bn=None, head=None
     stats, gamma, sums = bn if bn is not None else (None, None, None)
     dpred, whead = head if head is not None else (None, None)
     nvox = y.numel() // C
-    _lib.check(_sym('synthsr_elu_bwd_drop', y)(_lib.ptr(dy), _lib.ptr(dy2), _lib.ptr(y), _lib.ptr(out), _lib.ptr(dbias), nvox, C,
-                                        _lib.ptr(stats), _lib.ptr(gamma), eps, _lib.ptr(sums), _lib.ptr(dpred), _lib.ptr(whead),
-                                        _lib.ptr(drop), nvox // B, _lib.stream()), 'elu_bwd_drop')
+    _lib.check(_sym('synthsr_act_bwd_drop', y)(_lib.ptr(dy), _lib.ptr(dy2), _lib.ptr(y), _lib.ptr(out), _lib.ptr(dbias), nvox, C,
+                                               _lib.ptr(stats), _lib.ptr(gamma), eps, _lib.ptr(sums), _lib.ptr(dpred),
+                                               _lib.ptr(whead), _lib.ptr(drop), nvox // B, int(act), _lib.stream()),
+               'act_bwd_drop')
     return out
 
 
@@ -502,27 +505,26 @@ def bn_reduce_bwd(dy, x, stats, sums, eps=BN_EPS):
     return sums
 
 
-def bn_elu_bwd(dy, y, stats, gamma, sums, dy2=None, dbias=None, out=None, eps=BN_EPS):
-    """fused pass 2 of the BN backward + ELU backward (dy = gradient w.r.t. BN(y))"""
-    lib = _L()
+def bn_elu_bwd(dy, y, stats, gamma, sums, dy2=None, dbias=None, out=None, eps=BN_EPS, act=1):
+    """fused pass 2 of the BN backward + ELU (act 1) / ReLU (act 3) backward (dy = gradient w.r.t. BN(y))"""
     C = int(y.shape[-1])
     if out is None:
         out = torch.empty_like(y)
-    _lib.check(_sym('synthsr_bn_elu_bwd', y)(_lib.ptr(dy), _lib.ptr(dy2), _lib.ptr(y), _lib.ptr(out), _lib.ptr(dbias),
-                                      y.numel() // C, C, _lib.ptr(stats), _lib.ptr(gamma), eps, _lib.ptr(sums),
-                                      _lib.stream()), 'bn_elu_bwd')
+    _lib.check(_sym('synthsr_bn_act_bwd', y)(_lib.ptr(dy), _lib.ptr(dy2), _lib.ptr(y), _lib.ptr(out), _lib.ptr(dbias),
+                                             y.numel() // C, C, _lib.ptr(stats), _lib.ptr(gamma), eps, _lib.ptr(sums),
+                                             int(act), _lib.stream()), 'bn_act_bwd')
     return out
 
 
-def bn_pool_elu_bwd(dpool, y, stats, gamma, beta, sums, dy2=None, dbias=None, out=None, eps=BN_EPS):
+def bn_pool_elu_bwd(dpool, y, stats, gamma, beta, sums, dy2=None, dbias=None, out=None, eps=BN_EPS, act=1):
     """MaxPooling3D backward + BN backward (pass 2) + ELU backward of an encoder level in one pass: dpool = gradient w.r.t.
     maxpool(BN(y)), sums from bn_maxpool_bwd(..., out=False, sums=sums); bit-identical to bn_maxpool_bwd + bn_elu_bwd"""
     s = y.shape
     if out is None:
         out = torch.empty_like(y)
-    _lib.check(_sym('synthsr_bn_pool_elu_bwd', y)(_lib.ptr(dpool), _lib.ptr(y), _lib.ptr(dy2), _lib.ptr(out), _lib.ptr(dbias),
+    _lib.check(_sym('synthsr_bn_pool_act_bwd', y)(_lib.ptr(dpool), _lib.ptr(y), _lib.ptr(dy2), _lib.ptr(out), _lib.ptr(dbias),
                                                   _lib.i3(s[:3]), int(s[3]), _lib.ptr(stats), _lib.ptr(gamma), _lib.ptr(beta),
-                                                  _lib.ptr(sums), eps, _lib.stream()), 'bn_pool_elu_bwd')
+                                                  _lib.ptr(sums), eps, int(act), _lib.stream()), 'bn_pool_act_bwd')
     return out
 
 
@@ -753,15 +755,14 @@ def head_bwd(dpred, x, stats, gamma, beta, w, dbn, dw, db, eps=BN_EPS, bn_sums=N
     return dbn
 
 
-def bn_elu_bwd_head(dpred, whead, y, stats, gamma, sums, dbias=None, out=None, eps=BN_EPS):
+def bn_elu_bwd_head(dpred, whead, y, stats, gamma, sums, dbias=None, out=None, eps=BN_EPS, act=1):
     """bn_elu_bwd for the BN in front of the head: incoming gradient dpred[v]*whead[c] formed on the fly"""
-    lib = _L()
     C = int(y.shape[-1])
     if out is None:
         out = torch.empty_like(y)
-    _lib.check(_sym('synthsr_bn_elu_bwd_head', y)(_lib.ptr(dpred), _lib.ptr(whead), _lib.ptr(y), _lib.ptr(out),
-                                           _lib.ptr(dbias), y.numel() // C, C, _lib.ptr(stats), _lib.ptr(gamma), eps,
-                                           _lib.ptr(sums), _lib.stream()), 'bn_elu_bwd_head')
+    _lib.check(_sym('synthsr_bn_act_bwd_head', y)(_lib.ptr(dpred), _lib.ptr(whead), _lib.ptr(y), _lib.ptr(out),
+                                                  _lib.ptr(dbias), y.numel() // C, C, _lib.ptr(stats), _lib.ptr(gamma), eps,
+                                                  _lib.ptr(sums), int(act), _lib.stream()), 'bn_act_bwd_head')
     return out
 
 

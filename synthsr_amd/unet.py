@@ -62,8 +62,13 @@ class UNet3D:
         self._packed_scaled = False
         if conv_size != 3:
             raise NotImplementedError('only conv_size=3 is supported')
-        if activation != 'elu':
-            raise NotImplementedError("only activation='elu' is supported")
+        if activation not in ('elu', 'relu'):
+            raise NotImplementedError("activation should be 'elu' or 'relu'")
+        # the activation of every encoder / decoder conv (ext/neuron/models.py:316, 444; the head stays linear), as the conv
+        # epilogue codes of the library: forward (1 ELU, 3 ReLU) and the data gradient fused with it (2 x ELU', 4 x ReLU')
+        self.activation = activation
+        self._act = 1 if activation == 'elu' else 3
+        self._act_dgrad = self._act + 1
         if batch_norm not in (-1, len(input_shape) - 1 + 1, 4):
             raise NotImplementedError('batch_norm=-1 (channels-last BatchNormalization after each level) is required')
         # nb_labels > 1 / 'softmax': the (frozen) segmentation network of the segmentation-regularised loss
@@ -536,9 +541,9 @@ class UNet3D:
                 out = self.buf('enc%d_%d' % (l, k), self._bshape(l) + [c['cout']])
                 if self.training and k == nconv - 1 and self.batch == 1:  # the BatchNorm statistics ride in the conv epilogue
                     cur = ops.conv3d_stats(cur, c['wp'], self.view(c['b']), c['cout'], self._stats(e['bn']), self.bn_ws,
-                                           1, out=out)
+                                           self._act, out=out)
                 else:
-                    self._pb(lambda x_, o_, c=c: ops.conv3d(x_, c['wp'], self.view(c['b']), c['cout'], 1, out=o_), cur, out)
+                    self._pb(lambda x_, o_, c=c: ops.conv3d(x_, c['wp'], self.view(c['b']), c['cout'], self._act, out=o_), cur, out)
                     cur = out
                     if self.training and k == nconv - 1 and not per_sample:
                         ops.bn_stats(cur, self._stats(e['bn']), self.bn_ws)
@@ -572,7 +577,7 @@ class UNet3D:
 
                 def folded(lo_, skip_, o_, c0=c0):   # (bf16: the partial sums are rounded to bf16 once before the addition)
                     ops.conv3d_up(lo_, c0['wp_u'], None, None, c0['cout'], 0, out=o_)
-                    ops.conv3d_add(skip_, c0['wp_s'], self.view(c0['b']), o_, c0['cout'], 1, out=o_)
+                    ops.conv3d_add(skip_, c0['wp_s'], self.view(c0['b']), o_, c0['cout'], self._act, out=o_)
                 self._pb(folded, lo_bn, skip, cur)
                 acts.append(cur)
                 if per_sample:
@@ -592,10 +597,10 @@ class UNet3D:
                 out = self.buf('dec%d_%d' % (k, j), self._bshape(l) + [c['cout']])
                 if self.training and j == nconv - 1 and self.batch == 1:
                     cur = ops.conv3d_stats(cur, c['wp'], self.view(c['b']), c['cout'], self._stats(d['bn']), self.bn_ws,
-                                           1, out=out)
+                                           self._act, out=out)
                     stats_done = True
                 else:
-                    self._pb(lambda x_, o_, c=c: ops.conv3d(x_, c['wp'], self.view(c['b']), c['cout'], 1, out=o_), cur, out)
+                    self._pb(lambda x_, o_, c=c: ops.conv3d(x_, c['wp'], self.view(c['b']), c['cout'], self._act, out=o_), cur, out)
                     cur = out
                 acts.append(cur)
                 if per_sample:
@@ -948,7 +953,7 @@ class UNet3D:
         return g
 
     def _elu_backward(self, g, y, dy2, dbias, conv=None):
-        """ELU backward of a conv output y; consumes a pending BN backward (y was the BN input)"""
+        """activation (ELU / ReLU) backward of a conv output y; consumes a pending BN backward (y was the BN input)"""
         out = self.buf('dz', list(y.shape))
         pend, self._pending_bn = self._pending_bn, None
         if self._drop_ps is not None:  # per-sample dropout sits between y and its consumer
@@ -958,19 +963,21 @@ class UNet3D:
                 bn_args = (self._stats(pend[0]), self.view(pend[0]['gamma']), pend[1])
                 if g is None:
                     head = self._rank1
-            return ops.elu_bwd_drop(g, y, self._drop_ps[conv['name']], dy2=dy2, dbias=dbias, out=out, bn=bn_args, head=head)
+            return ops.elu_bwd_drop(g, y, self._drop_ps[conv['name']], dy2=dy2, dbias=dbias, out=out, bn=bn_args, head=head,
+                                    act=self._act)
         if pend is not None:
             bn, sums = pend[:2]
             if len(pend) > 2:  # g is the gradient w.r.t. the POOLED tensor: pool + BatchNorm + ELU backward in one pass
                 return ops.bn_pool_elu_bwd(g, y, self._stats(bn), self.view(bn['gamma']), self.view(bn['beta']), sums,
-                                           dy2=dy2, dbias=dbias, out=out)
+                                           dy2=dy2, dbias=dbias, out=out, act=self._act)
             if g is None:  # rank-1 gradient of the head
                 dpred, whead = self._rank1
                 assert dy2 is None
                 return ops.bn_elu_bwd_head(dpred, whead, y, self._stats(bn), self.view(bn['gamma']), sums, dbias=dbias,
-                                           out=out)
-            return ops.bn_elu_bwd(g, y, self._stats(bn), self.view(bn['gamma']), sums, dy2=dy2, dbias=dbias, out=out)
-        return ops.elu_bwd(g, y, dy2=dy2, dbias=dbias, out=out)
+                                           out=out, act=self._act)
+            return ops.bn_elu_bwd(g, y, self._stats(bn), self.view(bn['gamma']), sums, dy2=dy2, dbias=dbias, out=out,
+                                  act=self._act)
+        return ops.elu_bwd(g, y, dy2=dy2, dbias=dbias, out=out, act=self._act)
 
     def _convs_backward(self, g, g2, convs, acts, x_in, need_dx, tag, elu_below=None, below_conv=None, dacts=None):
         """g (+g2) = gradient w.r.t. the output of the last conv's ELU. Returns gradient w.r.t. x_in (or None);
@@ -1004,7 +1011,7 @@ class UNet3D:
                 # the activation instead of three; its dbias comes out of the weight-gradient GEMM
                 below = acts[j - 1] if j > 0 else elu_below
                 if below is not None:
-                    self._pb(lambda dz_, b_, o_: ops.conv3d_add(dz_, c['wpd'], None, b_, c['cin'], 2, out=o_), dz, below, out)
+                    self._pb(lambda dz_, b_, o_: ops.conv3d_add(dz_, c['wpd'], None, b_, c['cin'], self._act_dgrad, out=o_), dz, below, out)
                     if ps:  # the conv read s_b * ELU(below): the factor of the layer below's dropout on its gradient
                         ops.scale_channels(out, self._drop_ps[(convs[j - 1] if j > 0 else below_conv)['name']], out=out)
                     fused = True
