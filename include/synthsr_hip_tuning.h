@@ -35,7 +35,8 @@ int synthsr_split_tile_schedule(int kernel, int ntiles, int ny, int block_x, int
 int synthsr_set_deterministic(int on);
 /* The private dW planes of the deterministic weight-gradient flush are CALLER memory (torch allocates): `planes` = device
  * buffer of `bytes` on the current device, kept until replaced or withdrawn (NULL, 0); synchronises the device.  A weight
- * gradient that needs more than is registered returns SYNTHSR_EWORKSPACE and does nothing;
+ * gradient that needs more than is registered returns SYNTHSR_EWORKSPACE and does nothing (no launch, no memset: dW, dbias and
+ * dwc keep every bit -- tests/test_wgrad_scratch_gpu.py: test_too_small_planes_return_eworkspace_and_do_nothing);
  * synthsr_deterministic_workspace_demand() = the largest demand (bytes) any call on this device has had so far -- register
  * at least that much and call again (synthsr_amd/ops.py does exactly this).  The library itself allocates device memory in
  * ONE place: the ticket block + 64 MB of ordered-reduction scratch inside synthsr_set_deterministic(1). */

@@ -192,11 +192,16 @@ def load():
     return lib
 
 
-def check(rc, what=''):
+def check(rc, what='', planes=False):
+    """raises on a non-zero return code; planes: a -3 that is about the deterministic plane buffer, not the conv context"""
     if rc == 0:
         return
     if rc == -1:
         raise ValueError('synthsr_hip: invalid argument / unsupported shape in %s' % what)
+    if rc == -3 and planes:
+        raise SynthSRHipError('synthsr_hip: %s needs more deterministic weight-gradient planes than the registered plane buffer '
+                              'holds, even after registering a larger one (include/synthsr_hip_tuning.h: '
+                              'synthsr_set_deterministic_workspace)' % what)
     if rc == -3:
         raise SynthSRHipError('synthsr_hip: %s needs scratch and the conv context carries no (or too small a) workspace '
                               '(include/synthsr_hip.h: synthsr_conv_ctx.workspace)' % what)

@@ -3533,13 +3533,15 @@ int launch_wgrad(const float* in, const float* dout, float* dw, const int s[3], 
   if (auto once_ = attr_done.first()) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
   }
+  // planes first: a call that returns SYNTHSR_EWORKSPACE has launched NOTHING (the caller repeats it -- a column sum already
+  // added to dbias would be counted twice; tests/test_wgrad_scratch_gpu.py: test_too_small_planes_*)
+  float* no_dbias = nullptr;
+  if (const int rc_ = syn_det_prepare(&det, &dw, &no_dbias, dw_elems, Cout, gx, st)) return rc_;
+  ext.det_stride = det.stride;
   if (ext.dbias) {  // the generic kernel has no dbias row
     hipLaunchKernelGGL(colsum_kernel, dim3(1024), dim3(256), 0, st, dout, (int64_t)s[0] * s[1] * s[2], Cout, ext.dbias);
     if (hipGetLastError() != hipSuccess) return SYNTHSR_ELAUNCH;
   }
-  float* no_dbias = nullptr;
-  if (const int rc_ = syn_det_prepare(&det, &dw, &no_dbias, dw_elems, Cout, gx, st)) return rc_;
-  ext.det_stride = det.stride;
   hipLaunchKernelGGL(kern, dim3(gx, ncc * ymul, nco), dim3(256), smem, st, in, dout, dw, s[0], s[1], s[2], Cin, Cout,
                      tiles0, tiles1, tiles2, ext);
   if (hipGetLastError() != hipSuccess) return SYNTHSR_ELAUNCH;

@@ -137,26 +137,43 @@ _det_planes = {}    # device -> the torch buffer registered as the private dW pl
 
 def _register_det_planes(min_bytes):
     """the planes are CALLER memory (include/synthsr_hip_tuning.h: synthsr_set_deterministic_workspace): torch allocates, grown to
-    1.25x the library's recorded demand whenever a weight gradient reported SYNTHSR_EWORKSPACE"""
+    1.25x the library's recorded demand whenever a weight gradient reported SYNTHSR_EWORKSPACE.  Returns whether the
+    registration was short of that demand, i.e. whether a SYNTHSR_EWORKSPACE just reported was about the planes"""
     dev = torch.cuda.current_device()
-    want = max(int(min_bytes), int(1.25 * int(_L().synthsr_deterministic_workspace_demand())))
+    demand = int(_L().synthsr_deterministic_workspace_demand())
+    want = max(int(min_bytes), int(1.25 * demand))
     cur = _det_planes.get(dev)
-    if cur is None or cur.numel() < want:
-        torch.cuda.synchronize()
-        _det_planes[dev] = None     # release the old buffer before asking for the larger one
-        cur = torch.empty(want, dtype=torch.uint8, device='cuda:%d' % dev)
-        _det_planes[dev] = cur
-        _lib.check(_L().synthsr_set_deterministic_workspace(_lib.ptr(cur), cur.numel()), 'set_deterministic_workspace')
+    have = 0 if cur is None else cur.numel()
+    if have < want:
+        _resize_det_planes(want)
+    return have < demand
+
+
+def _resize_det_planes(nbytes):
+    """registers a fresh plane buffer of exactly `nbytes` on the current device (0: none) -- growth, and the tests that
+    shrink or withdraw the registration.  The library never holds a pointer torch may hand to another tensor: the old
+    registration is WITHDRAWN before the old buffer is released (released first: the two need not fit side by side), so an
+    allocation that raises leaves no planes registered and none recorded here, and the next weight gradient reports
+    SYNTHSR_EWORKSPACE and registers again (_check_wgrad; tests/test_wgrad_scratch_gpu.py:
+    test_failed_plane_allocation_leaves_no_stale_registration)"""
+    dev = torch.cuda.current_device()
+    _lib.check(_L().synthsr_set_deterministic_workspace(None, 0), 'set_deterministic_workspace')   # synchronises the device
+    _det_planes.pop(dev, None)
+    if nbytes:
+        new = torch.empty(int(nbytes), dtype=torch.uint8, device='cuda:%d' % dev)
+        _lib.check(_L().synthsr_set_deterministic_workspace(_lib.ptr(new), new.numel()), 'set_deterministic_workspace')
+        _det_planes[dev] = new
 
 
 def _check_wgrad(call, what):
     """weight-gradient launches: in deterministic mode the call may report that the registered plane buffer is too small
-    (nothing was launched) -- register a larger one and repeat ONCE"""
+    (nothing was launched: tests/test_wgrad_scratch_gpu.py) -- register a larger one and repeat ONCE"""
     rc = call()
+    short = False
     if rc == -3 and _deterministic:
-        _register_det_planes(0)
+        short = _register_det_planes(0)
         rc = call()
-    _lib.check(rc, what)
+    _lib.check(rc, what, planes=short)
 
 
 def deterministic_status():
@@ -357,7 +374,8 @@ def conv3d_up_dgrad(dout, wpacked8, Cl, out=None):
 def conv3d_up_wgrad(lo, dout, dwc, dw, ci_off, dwc_is_zero=False):
     """weight gradient of the up-sampled channel range: dwc [8,27,Cl,Cout] scratch, dw (+=).  dwc is zeroed here unless the
     caller vouches that it is all zeros (`dwc_is_zero`): the unpack kernel CONSUMES the partials and leaves zeros behind, so a
-    persistent scratch buffer needs the memset once, not once per call (UNet3D keeps that book)"""
+    persistent scratch buffer needs the memset once, not once per call (UNet3D keeps that book; every kernel variant:
+    tests/test_wgrad_scratch_gpu.py: test_dwc_is_all_zeros_after_unpack_and_reusable)"""
     lib = _L()
     s = lo.shape
     if not dwc_is_zero:

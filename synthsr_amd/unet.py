@@ -851,13 +851,19 @@ class UNet3D:
                     base = self._bufs['dwc']
                     known = getattr(self, '_dwc_zeroed', (None, 0))
                     dwc_is_zero = known[0] is base and known[1] >= dwc.numel()
-                    self._dwc_zeroed = (base, max(dwc.numel(), known[1] if known[0] is base else 0))
+                    zeroed = (base, max(dwc.numel(), known[1] if known[0] is base else 0))
 
-                    def c0_wgrads(skip=skip, dz=dz, dW=dW, lo_bn=lo_bn, dwc=dwc, c0=c0, Cs=Cs, dwc_is_zero=dwc_is_zero):
+                    def c0_wgrads(skip=skip, dz=dz, dW=dW, lo_bn=lo_bn, dwc=dwc, c0=c0, Cs=Cs, dwc_is_zero=dwc_is_zero,
+                                  zeroed=zeroed):
                         def one(skip_, dz_, lo_):
                             ops.conv3d_wgrad_part(skip_, dz_, dW, 0, dbias=self.view(c0['b'], self.grads))
                             ops.conv3d_up_wgrad(lo_, dz_, dwc, dW, Cs, dwc_is_zero=dwc_is_zero)
+                        # nothing is known about dwc while partials may sit in it: an exception between the weight gradient and
+                        # its unpack leaves the record empty and the next step zeroes the buffer again
+                        # (tests/test_wgrad_scratch_gpu.py: test_unet_zero_record_survives_an_interrupted_step)
+                        self._dwc_zeroed = (None, 0)
                         self._pb(one, skip, dz, lo_bn)
+                        self._dwc_zeroed = zeroed
                     self._fork(c0_wgrads, skip[..., 0].numel())
                 dskips[l] = self.buf('dskip%d' % l, self._bshape(l) + [Cs])
                 g = self.buf('dlo%d' % k, self._bshape(l + 1) + [Cl])
