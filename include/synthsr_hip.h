@@ -535,11 +535,15 @@ int synthsr_head_l1_fwd(const float* x, int64_t nvox, int C, const float* stats,
  *   0 'l1'  K=n  mean |pred - target|            1 'l2'  K=n  mean (pred - target)^2
  *   2 'laplace' K=2n (n intensity then n spread channels, training.py:325-326):
  *     mean( log(2b) + |pred_k - target_k| / b ),  b = 1e-5 + 0.02 exp(pred_{n+k})
- * (means over voxels and target channels; 1 <= K <= 4).  shape: the volume's 3 spatial sizes (host).  crop (host, NULL =
+ * (means over voxels and target channels; 1 <= K <= 16: up to 16 l1 / l2 targets or 8 laplace targets with their spreads;
+ * any other K returns SYNTHSR_EINVAL and launches nothing).  shape: the volume's 3 spatial sizes (host).  crop (host, NULL =
  * whole volume): {begin[3], size[3]} = the centred loss_cropping box (metrics_model.py:70-90): the mean runs over the
- * box, voxels outside get zero gradient.  residual (optional, [nvox][res_stride]): channel res_offs[k] (host, n entries)
- * is added to intensity channel k (work_with_residual_channel).  pred [nvox][K] (optional), dpred [nvox][K] (optional) =
- * dloss/dpred, loss: device float, zeroed by the caller. */
+ * box, voxels outside get zero gradient.  residual (optional, [nvox][res_stride]): channel res_offs[k] (host, one entry
+ * per target: n entries, up to 16) is added to intensity channel k (work_with_residual_channel).  pred [nvox][K]
+ * (optional), dpred [nvox][K] (optional) = dloss/dpred, loss: device float, zeroed by the caller.
+ * LDS: the kernel keeps 256 voxels x (C + 4) floats plus its coefficients in the 64 KB a launch gets by default.  K <= 4
+ * launches for C <= 48.  5 <= K <= 16 (two padded widths KB = 8 / 16: (2 + KB) C + KB + 256 (C + 4) floats plus 8 KB of
+ * static LDS) also fits for C <= 48 and returns SYNTHSR_EINVAL, before the launch, for anything wider. */
 int synthsr_head_loss_fwd(const float* x, const int shape[3], int C, const float* stats, const float* gamma,
                           const float* beta, float eps, const float* w, const float* b, int K, const float* residual,
                           int res_stride, const int* res_offs, const float* target, float* pred, float* dpred,
@@ -576,7 +580,8 @@ int synthsr_ssim_point(const float* filtered, int64_t nq, float max_val, float s
                        synthsr_stream_t stream);
 int synthsr_ssim_combine(const float* gback, const float* pred, const float* target, const int shape[3], const int* crop,
                          float* dpred, synthsr_stream_t stream);
-/* backward of a K-channel head (2 <= K <= 4): dbn[v][c] = sum_k dpred[v][k]*w[c][k] (written), dw [C][K] +=, db [K] += */
+/* backward of a K-channel head (2 <= K <= 16; any other K returns SYNTHSR_EINVAL and launches nothing):
+ * dbn[v][c] = sum_k dpred[v][k]*w[c][k] (written), dw [C][K] +=, db [K] += */
 int synthsr_head_bwd_multi(const float* dpred, const float* x, int64_t nvox, int C, int K, const float* stats,
                            const float* gamma, const float* beta, float eps, const float* w, float* dbn, float* dw,
                            float* db, synthsr_stream_t stream);

@@ -658,7 +658,7 @@ __global__ __launch_bounds__(256) void upsample_concat_bwd_kernel(const T* __res
 struct HeadBox {
   int on, d1, d2;
   int lo[3], hi[3];
-  int res_off[4];  // residual channel added to intensity channel k (work_with_residual_channel)
+  int res_off[16];  // residual channel added to intensity channel k (work_with_residual_channel)
 };
 
 // CT = 24 (round 6): the 24-feature head of the benchmark network keeps the 72 BatchNorm / head coefficients of its dot product in
@@ -957,6 +957,295 @@ __global__ __launch_bounds__(RB) void head_multi_bwd_kernel(const float* __restr
       atomicAdd(&dw[i], gamma[c] * smem[k * C + c] + beta[c] * smem[K * C + k]);
     }
     if (threadIdx.x < K) atomicAdd(&db[threadIdx.x], smem[K * C + threadIdx.x]);
+  }
+  syn_det_gather_end(K * C + K);
+}
+
+// ------------------------------------------------------------------------------------------ wide heads (5 <= K <= 16)
+// training(output_channel=[...]) with five or more l1 / l2 targets, or three or more 'laplace' targets (intensity + spread
+// channel each).  Two padded widths KB in {8, 16} serve every K <= KB at run time: the per-voxel arrays have KB elements and are
+// indexed statically (registers, no scratch); the weight and bias slots k >= K are zero in LDS, so the padded lanes compute
+// zeros, and every access to pred / dpred / target / residual is guarded by the real K.  Same contracts, same order of the
+// products and the same deterministic-mode gather (of the real K C + K values) as the K <= 4 kernels above.
+
+// a[k] <- a[k + s] (zeros shifted in), 0 <= s < N: a barrel shifter of wave-uniform steps, so that the spread channel NT + k of
+// a 'laplace' head with a run-time number of targets NT is reached without a dynamic register index
+template <int N>
+__device__ __forceinline__ void shift_down(float (&a)[N], int s) {
+#pragma unroll
+  for (int bit = 1; bit < N; bit <<= 1) {
+    if (s & bit) {
+#pragma unroll
+      for (int k = 0; k < N; ++k) a[k] = (k + bit < N) ? a[k + bit] : 0.f;
+    }
+  }
+}
+// a[k] <- a[k - s]
+template <int N>
+__device__ __forceinline__ void shift_up(float (&a)[N], int s) {
+#pragma unroll
+  for (int bit = 1; bit < N; bit <<= 1) {
+    if (s & bit) {
+#pragma unroll
+      for (int k = N - 1; k >= 0; --k) a[k] = (k - bit >= 0) ? a[k - bit] : 0.f;
+    }
+  }
+}
+
+// head_loss_fwd_kernel for K <= KB channels.  vec4: K % 4 == 0 and pred / dpred are 16-byte aligned -- a voxel's K values
+// are then stored as float4.  Dynamic LDS: scale[C], shift[C], w[KB][C], b[KB], then the voxel tile.
+template <typename T, int KB>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void head_loss_fwd_wide_kernel(const T* __restrict__ x, int64_t nvox, int C,
+                                                                 const float* __restrict__ stats,
+                                                                 const float* __restrict__ gamma,
+                                                                 const float* __restrict__ beta, float eps,
+                                                                 const float* __restrict__ w, const float* __restrict__ b,
+                                                                 int K, const float* __restrict__ residual, int rs,
+                                                                 const float* __restrict__ target,
+                                                                 float* __restrict__ pred, float* __restrict__ dpred,
+                                                                 float* __restrict__ loss, float inv_n, int kind,
+                                                                 HeadBox box, int vec4) {
+  const int NT = kind == 2 ? K / 2 : K;  // regression targets
+  extern __shared__ float smem[];
+  float* weff = smem;
+  float* wl = smem + 2 * C;
+  float* bl = wl + KB * C;
+  for (int c = threadIdx.x; c < C; c += blockDim.x) {
+    float sc, sh;
+    bn_coeff(stats, gamma, beta, eps, C, c, sc, sh);
+    weff[c] = sc;
+    weff[C + c] = sh;
+#pragma unroll
+    for (int k = 0; k < KB; ++k) wl[k * C + c] = k < K ? w[c * K + k] : 0.f;
+  }
+  if ((int)threadIdx.x < KB) bl[threadIdx.x] = (int)threadIdx.x < K ? b[threadIdx.x] : 0.f;
+  __syncthreads();
+  float lsum = 0.f;
+  float* tile = bl + KB;
+  const int C4 = C / 4, CP = C + 4;
+  constexpr int PF = 8;  // float4 per thread of a prefetched slab (see head_loss_fwd_kernel)
+  const bool prefetch = C4 <= PF;
+  float4 nxt[PF];
+  auto fetch = [&](int64_t v0n) {
+    const int nvn = v0n < nvox ? (int)min((int64_t)256, nvox - v0n) : 0;
+#pragma unroll
+    for (int k = 0; k < PF; ++k) {
+      const int i = (int)threadIdx.x + 256 * k;
+      if (k < C4 && i < nvn * C4) nxt[k] = ld4(x + v0n * C + (int64_t)i * 4);
+    }
+  };
+  if (prefetch) fetch((int64_t)blockIdx.x * 256);
+  for (int64_t v0 = (int64_t)blockIdx.x * 256; v0 < nvox; v0 += (int64_t)gridDim.x * 256) {
+    const int nv = (int)min((int64_t)256, nvox - v0);
+    __syncthreads();
+    if (prefetch) {
+#pragma unroll
+      for (int k = 0; k < PF; ++k) {
+        const int i = (int)threadIdx.x + 256 * k;
+        if (k < C4 && i < nv * C4) {
+          const int vl = i / C4, q = i - vl * C4;
+          *reinterpret_cast<float4*>(&tile[vl * CP + q * 4]) = nxt[k];
+        }
+      }
+      fetch(v0 + (int64_t)gridDim.x * 256);
+    } else {
+      for (int i = threadIdx.x; i < nv * C4; i += 256) {
+        const int vl = i / C4, q = i - vl * C4;
+        *reinterpret_cast<float4*>(&tile[vl * CP + q * 4]) = ld4(x + v0 * C + (int64_t)i * 4);
+      }
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < nv) {
+      const int64_t v = v0 + threadIdx.x;
+      float acc[KB];
+#pragma unroll
+      for (int k = 0; k < KB; ++k) acc[k] = 0.f;
+      const float* xp = tile + threadIdx.x * CP;
+#pragma unroll 1
+      for (int c = 0; c < C; c += 4) {  // (not unrolled: 4 KB independent products per trip already)
+        const float4 a = *reinterpret_cast<const float4*>(xp + c);
+        const float n0 = a.x * weff[c + 0] + weff[C + c + 0], n1 = a.y * weff[c + 1] + weff[C + c + 1];
+        const float n2 = a.z * weff[c + 2] + weff[C + c + 2], n3 = a.w * weff[c + 3] + weff[C + c + 3];
+#pragma unroll
+        for (int k = 0; k < KB; ++k) {
+          const float4 wk = *reinterpret_cast<const float4*>(wl + k * C + c);
+          acc[k] += wk.x * n0;
+          acc[k] += wk.y * n1;
+          acc[k] += wk.z * n2;
+          acc[k] += wk.w * n3;
+        }
+      }
+#pragma unroll
+      for (int k = 0; k < KB; ++k) acc[k] += bl[k];
+      if (residual) {
+#pragma unroll
+        for (int k = 0; k < KB; ++k)
+          if (k < NT) acc[k] += residual[v * rs + box.res_off[k]];
+      }
+      if (pred) {
+        if (vec4) {
+#pragma unroll
+          for (int k = 0; k < KB; k += 4)
+            if (k < K) st4(pred + v * K + k, make_float4(acc[k], acc[k + 1], acc[k + 2], acc[k + 3]));
+        } else {
+#pragma unroll
+          for (int k = 0; k < KB; ++k)
+            if (k < K) pred[v * K + k] = acc[k];
+        }
+      }
+      bool inside = true;
+      if (box.on) {
+        const int xx = (int)(v % box.d2), yy = (int)((v / box.d2) % box.d1), zz = (int)(v / ((int64_t)box.d1 * box.d2));
+        inside = zz >= box.lo[0] && zz < box.hi[0] && yy >= box.lo[1] && yy < box.hi[1] && xx >= box.lo[2] && xx < box.hi[2];
+      }
+      float g[KB];
+#pragma unroll
+      for (int k = 0; k < KB; ++k) g[k] = 0.f;
+      if (inside) {
+        if (kind == 2) {  // laplace: the spread of target k is channel NT + k
+          float sp[KB], gs[KB];
+#pragma unroll
+          for (int k = 0; k < KB; ++k) {
+            sp[k] = acc[k];
+            gs[k] = 0.f;
+          }
+          shift_down<KB>(sp, NT);
+#pragma unroll
+          for (int k = 0; k < KB / 2; ++k) {
+            if (k < NT) {
+              const float e = acc[k] - target[v * NT + k];
+              const float sgn = e > 0.f ? 1.f : (e < 0.f ? -1.f : 0.f);
+              const float ex = 0.02f * expf(sp[k]), bb = 1e-5f + ex, ib = 1.f / bb;
+              lsum += logf(2.f * bb) + fabsf(e) * ib;
+              g[k] = sgn * ib * inv_n;
+              gs[k] = (ib - fabsf(e) * ib * ib) * ex * inv_n;
+            }
+          }
+          shift_up<KB>(gs, NT);
+#pragma unroll
+          for (int k = 0; k < KB; ++k)
+            if (k >= NT) g[k] = gs[k];
+        } else {
+#pragma unroll
+          for (int k = 0; k < KB; ++k) {
+            if (k < NT) {
+              const float e = acc[k] - target[v * NT + k];
+              if (kind == 1) {
+                lsum += e * e;
+                g[k] = 2.f * e * inv_n;
+              } else {
+                lsum += fabsf(e);
+                g[k] = (e > 0.f ? 1.f : (e < 0.f ? -1.f : 0.f)) * inv_n;
+              }
+            }
+          }
+        }
+      }
+      if (dpred) {
+        if (vec4) {
+#pragma unroll
+          for (int k = 0; k < KB; k += 4)
+            if (k < K) st4(dpred + v * K + k, make_float4(g[k], g[k + 1], g[k + 2], g[k + 3]));
+        } else {
+#pragma unroll
+          for (int k = 0; k < KB; ++k)
+            if (k < K) dpred[v * K + k] = g[k];
+        }
+      }
+    }
+  }
+  // one atomic per workgroup on the loss word, as in head_loss_fwd_kernel
+  lsum = syn_wave_sum(lsum);
+  __shared__ float wsum[4];
+  if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = lsum;
+  __syncthreads();
+  if (threadIdx.x == 0) wsum[0] = (wsum[0] + wsum[1] + wsum[2] + wsum[3]) * inv_n;
+  __syncthreads();
+  if (syn_det_gather(wsum, 1))
+    if (threadIdx.x == 0) atomicAdd(loss, wsum[0]);
+  syn_det_gather_end(1);
+}
+
+// head_multi_bwd_kernel for K <= KB channels.  vec4: K % 4 == 0 and dpred is 16-byte aligned.  Dynamic LDS: A[KB][C], B[KB],
+// then the head weights as w[KB][C] (one 16-byte read per channel quad and k; rows k >= K zero).
+template <typename T, int KB>
+__global__ __launch_bounds__(RB) void head_multi_bwd_wide_kernel(const float* __restrict__ dpred, const T* __restrict__ x,
+                                                                 int64_t n4, int C, int K, const float* __restrict__ stats,
+                                                                 const float* __restrict__ gamma,
+                                                                 const float* __restrict__ beta, float eps,
+                                                                 const float* __restrict__ w, T* __restrict__ dbn,
+                                                                 float* __restrict__ dw, float* __restrict__ db, int vec4) {
+  extern __shared__ float smem[];
+  float* wl = smem + KB * C + KB;
+  const int C4 = C / 4;
+  const bool fixed = (RB % C4) == 0;
+  for (int i = threadIdx.x; i < KB * C + KB; i += RB) smem[i] = 0.f;
+  for (int i = threadIdx.x; i < KB * C; i += RB) {
+    const int k = i / C, c = i - k * C;
+    wl[i] = k < K ? w[c * K + k] : 0.f;
+  }
+  __syncthreads();
+  float4 part[KB];
+  float dbp[KB];
+#pragma unroll
+  for (int k = 0; k < KB; ++k) {
+    part[k] = make_float4(0.f, 0.f, 0.f, 0.f);
+    dbp[k] = 0.f;
+  }
+  const int64_t stride = (int64_t)gridDim.x * RB;
+  for (int64_t i = blockIdx.x * (int64_t)RB + threadIdx.x; i < n4; i += stride) {
+    const int c = (int)(i % C4) * 4;
+    const int64_t v = i / C4;
+    const float4 a = ld4(x + i * 4);
+    float4 xh;
+    xh.x = (a.x - stats[c + 0]) * rsqrtf(stats[C + c + 0] + eps);
+    xh.y = (a.y - stats[c + 1]) * rsqrtf(stats[C + c + 1] + eps);
+    xh.z = (a.z - stats[c + 2]) * rsqrtf(stats[C + c + 2] + eps);
+    xh.w = (a.w - stats[c + 3]) * rsqrtf(stats[C + c + 3] + eps);
+    float4 d = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+    for (int k0 = 0; k0 < KB; k0 += 4) {  // four channels at a time: only their four gradients are live
+      float g[4];
+      if (vec4) {
+        const float4 t = k0 < K ? ld4(dpred + v * K + k0) : make_float4(0.f, 0.f, 0.f, 0.f);
+        g[0] = t.x; g[1] = t.y; g[2] = t.z; g[3] = t.w;
+      } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) g[j] = k0 + j < K ? dpred[v * K + k0 + j] : 0.f;
+      }
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int k = k0 + j;
+        const float4 wk = *reinterpret_cast<const float4*>(wl + k * C + c);
+        d.x += g[j] * wk.x; d.y += g[j] * wk.y;
+        d.z += g[j] * wk.z; d.w += g[j] * wk.w;
+        if (fixed) {
+          part[k].x += g[j] * xh.x; part[k].y += g[j] * xh.y; part[k].z += g[j] * xh.z; part[k].w += g[j] * xh.w;
+        } else if (k < K) {
+          atomicAdd(&smem[k * C + c + 0], g[j] * xh.x); atomicAdd(&smem[k * C + c + 1], g[j] * xh.y);
+          atomicAdd(&smem[k * C + c + 2], g[j] * xh.z); atomicAdd(&smem[k * C + c + 3], g[j] * xh.w);
+        }
+        if (c == 0) dbp[k] += g[j];
+      }
+    }
+    st4(dbn + i * 4, d);
+  }
+#pragma unroll
+  for (int k = 0; k < KB; ++k)
+    if (k < K) block_scalar_add(dbp[k], &smem[KB * C + k]);
+  block_channel_reduce<KB>(part, threadIdx.x % C4, C4, fixed, smem);
+  if (K < KB) {  // the gather takes A[K][C] | B[K] of the real K: move B up behind the last real row of A
+    const float bv = (int)threadIdx.x < K ? smem[KB * C + threadIdx.x] : 0.f;
+    __syncthreads();
+    if ((int)threadIdx.x < K) smem[K * C + threadIdx.x] = bv;
+    __syncthreads();
+  }
+  if (syn_det_gather(smem, K * C + K)) {
+    for (int i = threadIdx.x; i < C * K; i += RB) {
+      const int c = i / K, k = i - c * K;
+      atomicAdd(&dw[i], gamma[c] * smem[k * C + c] + beta[c] * smem[K * C + k]);
+    }
+    if ((int)threadIdx.x < K) atomicAdd(&db[threadIdx.x], smem[K * C + threadIdx.x]);
   }
   syn_det_gather_end(K * C + K);
 }
@@ -1311,12 +1600,12 @@ int head_loss_fwd_t(const T* x, const int* shape, int C, const float* stats, con
   if (!x || !shape || !stats || !gamma || !beta || !w || !b || !target || !loss || !ok_c4(C)) return SYNTHSR_EINVAL;
   if (ab && (K != 1 || kind == 2 || C > 120)) return SYNTHSR_EINVAL;  // the fused backward sums exist for the 1-channel l1 / l2 head
   if (shape[0] < 1 || shape[1] < 1 || shape[2] < 1) return SYNTHSR_EINVAL;
-  if (kind < 0 || kind > 2 || K < 1 || K > 4 || (kind == 2 && (K & 1))) return SYNTHSR_EINVAL;
+  if (kind < 0 || kind > 2 || K < 1 || K > 16 || (kind == 2 && (K & 1))) return SYNTHSR_EINVAL;
   const int NT = kind == 2 ? K / 2 : K;
   if (C > 116) return SYNTHSR_EINVAL;  // LDS: (2 + K) C + 256 (C + 4) floats
   const int64_t nvox = (int64_t)shape[0] * shape[1] * shape[2];
   HeadBox box;
-  for (int k = 0; k < 4; ++k) box.res_off[k] = 0;
+  for (int k = 0; k < 16; ++k) box.res_off[k] = 0;
   if (residual) {
     if (res_stride < 1 || !res_offs) return SYNTHSR_EINVAL;
     for (int k = 0; k < NT; ++k) {
@@ -1359,7 +1648,32 @@ int head_loss_fwd_t(const T* x, const int* shape, int C, const float* stats, con
       break;
     case 2: SYN_HEAD_FWD(2); break;
     case 3: SYN_HEAD_FWD(3); break;
-    default: SYN_HEAD_FWD(4); break;
+    case 4: SYN_HEAD_FWD(4); break;
+    default: {  // 5 <= K <= 16: the padded kernels
+      // LDS rule of the wide heads: ((2 + KB) C + KB + 256 (C + 4)) floats of dynamic LDS (KB = 8 for K <= 8, else 16) plus the
+      // kernel's static LDS (the deterministic gather's column buffer, 8 KB) must fit the 64 KB a launch gets without an
+      // attribute: C <= 48 at both widths, which is also the largest C that launches at K <= 4.  Anything wider is refused
+      // here, before the launch.
+      const int KB = K <= 8 ? 8 : 16;
+      const size_t smem_w = ((size_t)(2 + KB) * C + KB + 256 * (size_t)(C + 4)) * sizeof(float);
+      const void* fn = KB == 8 ? (const void*)head_loss_fwd_wide_kernel<T, 8> : (const void*)head_loss_fwd_wide_kernel<T, 16>;
+      static size_t static_lds[2] = {0, 0};  // per width; the same on every device
+      size_t& st = static_lds[KB == 8 ? 0 : 1];
+      if (st == 0) {
+        hipFuncAttributes fa;
+        if (hipFuncGetAttributes(&fa, fn) != hipSuccess) return SYNTHSR_ELAUNCH;
+        st = fa.sharedSizeBytes > 0 ? fa.sharedSizeBytes : 1;
+      }
+      if (smem_w + st > 65536) return SYNTHSR_EINVAL;
+      const int vec4 = (K % 4 == 0) && ((uintptr_t)pred % 16 == 0) && ((uintptr_t)dpred % 16 == 0);
+      if (KB == 8)
+        hipLaunchKernelGGL((head_loss_fwd_wide_kernel<T, 8>), grid, dim3(256), smem_w, (hipStream_t)stream, x, nvox, C, stats, gamma,
+                           beta, eps, w, b, K, residual, res_stride, target, pred, dpred, loss, inv_n, kind, box, vec4);
+      else
+        hipLaunchKernelGGL((head_loss_fwd_wide_kernel<T, 16>), grid, dim3(256), smem_w, (hipStream_t)stream, x, nvox, C, stats, gamma,
+                           beta, eps, w, b, K, residual, res_stride, target, pred, dpred, loss, inv_n, kind, box, vec4);
+      break;
+    }
   }
 #undef SYN_HEAD_FWD
   SYN_CHECK_LAUNCH();
@@ -1368,7 +1682,7 @@ int head_loss_fwd_t(const T* x, const int* shape, int C, const float* stats, con
 
 template <typename T>
 int head_bwd_multi_t(const float* dpred, const T* x, int64_t nvox, int C, int K, const float* stats, const float* gamma, const float* beta, float eps, const float* w, T* dbn, float* dw, float* db, synthsr_stream_t stream) {
-  if (!dpred || !x || !stats || !gamma || !beta || !w || !dbn || !dw || !db || nvox < 1 || !ok_c4(C) || K < 2 || K > 4)
+  if (!dpred || !x || !stats || !gamma || !beta || !w || !dbn || !dw || !db || nvox < 1 || !ok_c4(C) || K < 2 || K > 16)
     return SYNTHSR_EINVAL;
   const int64_t n4 = nvox * (C / 4);
   const dim3 grid(syn_grid(n4, RB, head_grid()));
@@ -1379,7 +1693,20 @@ int head_bwd_multi_t(const float* dpred, const T* x, int64_t nvox, int C, int K,
   switch (K) {
     case 2: SYN_HEAD_BWD(2); break;
     case 3: SYN_HEAD_BWD(3); break;
-    default: SYN_HEAD_BWD(4); break;
+    case 4: SYN_HEAD_BWD(4); break;
+    default: {  // 5 <= K <= 16: the padded kernels; LDS A[KB][C] | B[KB] | w[KB][C]
+      const int KB = K <= 8 ? 8 : 16;
+      const size_t smem_w = ((size_t)2 * KB * C + KB) * sizeof(float);
+      if (smem_w > 48 * 1024) return SYNTHSR_EINVAL;  // C <= 380 at KB = 16; the forward kernel stops far below
+      const int vec4 = (K % 4 == 0) && ((uintptr_t)dpred % 16 == 0);
+      if (KB == 8)
+        hipLaunchKernelGGL((head_multi_bwd_wide_kernel<T, 8>), grid, dim3(RB), smem_w, (hipStream_t)stream, dpred, x, n4, C, K, stats,
+                           gamma, beta, eps, w, dbn, dw, db, vec4);
+      else
+        hipLaunchKernelGGL((head_multi_bwd_wide_kernel<T, 16>), grid, dim3(RB), smem_w, (hipStream_t)stream, dpred, x, n4, C, K, stats,
+                           gamma, beta, eps, w, dbn, dw, db, vec4);
+      break;
+    }
   }
 #undef SYN_HEAD_BWD
   SYN_CHECK_LAUNCH();

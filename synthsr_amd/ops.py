@@ -648,7 +648,7 @@ def head_loss_fwd(x, stats, gamma, beta, w, b, target, loss, kind='l1', crop=Non
     """unet_likelihood + regression loss (metrics_model.py:30-132).  x [d0,d1,d2,C]; w [C,K]; target [nvox*n] for n
     regression targets: K = n ('l1', 'l2') or 2n ('laplace': intensities then spreads); crop = (begin[3], size[3]) of the
     loss_cropping box or None; residual [nvox, res_stride] with res_off = the channel (or one per target) added to the
-    intensities; pred / dpred [nvox*K]"""
+    intensities; pred / dpred [nvox*K].  1 <= K <= 16 (16 l1 / l2 targets, or 8 laplace targets with their spreads)"""
     lib = _L()
     C = int(x.shape[-1])
     if x.dim() != 4:
@@ -656,7 +656,7 @@ def head_loss_fwd(x, stats, gamma, beta, w, b, target, loss, kind='l1', crop=Non
     K = w.numel() // C
     nvox = x.numel() // C
     n = K // 2 if kind == 'laplace' else K
-    if w.numel() != C * K or K < 1 or K > 4 or (kind == 'laplace' and K % 2) or target.numel() != nvox * n:
+    if w.numel() != C * K or K < 1 or K > 16 or (kind == 'laplace' and K % 2) or target.numel() != nvox * n:
         raise ValueError('head with %d output channels / target of %d values do not fit the %s loss on %d voxels'
                          % (K, target.numel(), kind, nvox))
     shape = _lib.I3(*[int(v) for v in x.shape[:3]])
@@ -674,7 +674,7 @@ def head_loss_fwd(x, stats, gamma, beta, w, b, target, loss, kind='l1', crop=Non
                                                       _lib.ptr(target), _lib.ptr(pred), _lib.ptr(dpred), _lib.ptr(loss),
                                                       LOSS_KINDS[kind], box, _lib.ptr(ab), _lib.stream()), 'head_loss_fwd_ab')
         return loss
-    offs = (_lib.c_int * 4)(*(offs + [0] * (4 - n)))
+    offs = (_lib.c_int * 16)(*(offs + [0] * (16 - n)))
     _lib.check(_sym('synthsr_head_loss_fwd', x)(_lib.ptr(x), shape, C, _lib.ptr(stats), _lib.ptr(gamma), _lib.ptr(beta), eps,
                                          _lib.ptr(w), _lib.ptr(b), K, _lib.ptr(residual), int(res_stride), offs,
                                          _lib.ptr(target), _lib.ptr(pred), _lib.ptr(dpred), _lib.ptr(loss),
@@ -751,11 +751,14 @@ def head_bwd_from_sums(ab, gamma, beta, w, dw, db, bn_sums=None):
 
 
 def head_bwd_multi(dpred, x, stats, gamma, beta, w, dbn, dw, db, eps=BN_EPS):
-    """K-channel head backward (2 <= K <= 4): dbn = dpred @ w^T written, dw [C,K] and db [K] accumulated"""
+    """K-channel head backward (2 <= K <= 16): dbn = dpred @ w^T written, dw [C,K] and db [K] accumulated"""
     lib = _L()
     C = int(x.shape[-1])
     nvox = x.numel() // C
     K = w.numel() // C
+    if w.numel() != C * K or K < 2 or K > 16 or dpred.numel() != nvox * K:
+        raise ValueError('head_bwd_multi takes a head of 2 to 16 output channels and dpred [nvox * K] (K = %d, dpred of %d '
+                         'values on %d voxels)' % (K, dpred.numel(), nvox))
     _lib.check(_sym('synthsr_head_bwd_multi', x)(_lib.ptr(dpred), _lib.ptr(x), nvox, C, K, _lib.ptr(stats), _lib.ptr(gamma),
                                           _lib.ptr(beta), eps, _lib.ptr(w), _lib.ptr(dbn), _lib.ptr(dw), _lib.ptr(db),
                                           _lib.stream()), 'head_bwd_multi')

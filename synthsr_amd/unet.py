@@ -79,8 +79,8 @@ class UNet3D:
         # 'laplace' loss (SynthSR/training.py:246-249, 325-326)
         if final_pred_activation == 'softmax' and nb_labels < 2:
             raise NotImplementedError('a softmax head needs nb_labels > 1')
-        if final_pred_activation == 'linear' and not 1 <= nb_labels <= 4:
-            raise NotImplementedError('linear heads have 1 to 4 output channels')
+        if final_pred_activation == 'linear' and not 1 <= nb_labels <= 16:
+            raise NotImplementedError('linear heads have 1 to 16 output channels')
         self.final_pred_activation = final_pred_activation
         self.nb_labels = int(nb_labels)
         self.need_input_grad = False  # True: also keep the data-gradient weights of the first conv (backward_input)
