@@ -264,21 +264,23 @@ int synthsr_conv3d_wgrad_ex(const synthsr_conv_ctx* ctx, const float* in, const 
 
 /* launch geometry the kernels will use: out = {chunk width CK, #ci chunks, n-tiles per workgroup (0: 4x4x1-MFMA layout of
  * the Cout = 24 layers, -Cin: first-layer layout), #n chunks, MT, ksplit (split arithmetic: 2 = the 512-thread split-K-halves
- * kernel of the layers that leave CUs single-occupied), NV, floats per packed weight set}.
+ * kernel of the layers that leave CUs single-occupied), reserved (out[6], always written as 0), floats per packed weight
+ * set}.
  * kind: 1 plain conv; 2 forward parity convs of a folded decoder conv; 0 their data gradient */
 int synthsr_conv3d_plan(const synthsr_conv_ctx* ctx, const int shape[3], int CinE, int CoutE, int kind, int64_t out[8]);
 /* 1 / 0: whether the weight gradient of a plain 3x3x3 conv of this shape runs on the split kernels under this context (the
  * dispatcher's own condition) -- what benchmarks price a layer against.  Negative: SYNTHSR_EINVAL. */
 int synthsr_conv3d_wgrad_runs_split(const synthsr_conv_ctx* ctx, const int shape[3], int Cin, int Cout);
 /* packs every layer of a network in ONE launch.  jobs_dev: int64 [njobs][14] = {w_off, dst_off, count, cin_total,
- * ci_off, cin, cout, mode, ck, ncc, nt, parity(-1 plain), nv, mfma_count}; w_off / dst_off are float offsets.
+ * ci_off, cin, cout, mode, ck, ncc, nt, parity(-1 plain), reserved, nchunks}; w_off / dst_off are float offsets.  The 13th
+ * int64 of a record is reserved and ignored; the 14th (the plan's #n chunks) is read for the split layouts only (nt <= -100).
  * `packed` must have been ZEROED once by the caller: of a 27-slot parity set (parity 0..7, nt > 0) only the 8 slots of the
  * parity's 2x2x2 window are written, the structurally empty 19 are left as they are */
 int synthsr_conv3d_pack_all(const float* params, float* packed, const int64_t* jobs_dev, int njobs,
                             synthsr_stream_t stream);
 
 /* (rounds 1-4 had a process-wide option switch and a process-wide arithmetic setter behind these kernels; both are gone --
- * plan parameters are constants of the library, the arithmetic travels in synthsr_conv_ctx.  What is left in
+ * a launch plan is a pure function of its arguments, the arithmetic travels in synthsr_conv_ctx.  What is left in
  * synthsr_hip_tuning.h: the deterministic TEST mode and a host-only tile-schedule query.) */
 
 /* ---- bf16 twins of the HBM-bound U-Net kernels: same arguments and semantics as the float32 entry point of the same

@@ -125,7 +125,7 @@ __device__ __forceinline__ float weight_value(const float* __restrict__ w, int t
 // of the parity's 2x2x2 window (syn_split_tap8); the kernel reads tap (a, b, c) at halo offset (1 - p) + a per axis (UPM 2:
 // folded data gradient, or a stride-2 forward, parity code 8 + p) or a + p (the forward kernel conv3d_split_upfwd_kernel) --
 // that offset IS the 27-slot index weight_value folds the original taps onto, whatever the orientation (`mode`) of the set.
-// `nchunks` (the job's mfma_count field) = number of co-chunks.
+// `nchunks` (the 14th field of a pack_all job) = number of co-chunks.
 __host__ __device__ inline int64_t split_plane_floats(int NT, int ncc, int nchunks) {  // floats of one piece plane
   const int MT = NT <= -300 ? -300 - NT : (NT <= -200 ? -200 - NT : -100 - NT);
   return (int64_t)nchunks * ncc * (NT <= -200 ? 2 : 7) * MT * 64 * 4;
@@ -195,16 +195,15 @@ __device__ __forceinline__ float stacked_pack_value(const float* __restrict__ w,
   return __uint_as_float(pc[piece]);
 }
 
-// packed layout of one weight set: MFMA section [nc][cc][tap][cg][nt][lane][2] (B fragments), followed — when the layer
-// keeps NV output channels on the vector ALUs — by the VALU section [cc][tap][ci (CK)][NV] (wave-uniform scalar loads)
+// packed layout of one weight set, selected by NT (FwdPlan::pack_nt); NT > 0: [nc][cc][tap][cg][nt][lane][2] (B fragments).
+// `nchunks` is read by the split layouts only (their number of co-chunks).
 __device__ __forceinline__ float pack_value(const float* __restrict__ w, int64_t idx, int Cin_total, int ci_off, int Cin,
-                                            int Cout, int mode, int CK, int ncc, int NT, int parity, int NV,
-                                            int64_t mfma_count) {
+                                            int Cout, int mode, int CK, int ncc, int NT, int parity, int nchunks) {
   if (NT == -400) return stacked_pack_value(w, idx, Cin_total, ci_off, Cin, Cout, mode);
   if (NT <= -100) {  // split layouts: one piece of split_pack_pair
-    const int64_t n3 = split_plane_floats(NT, ncc, (int)mfma_count);
+    const int64_t n3 = split_plane_floats(NT, ncc, nchunks);
     uint32_t pc[3];
-    split_pack_pair(w, idx % n3, Cin_total, ci_off, Cin, Cout, mode, ncc, NT, parity, (int)mfma_count, pc);
+    split_pack_pair(w, idx % n3, Cin_total, ci_off, Cin, Cout, mode, ncc, NT, parity, nchunks, pc);
     return __uint_as_float(pc[idx / n3]);
   }
   if (NT < 0) {
@@ -234,17 +233,6 @@ __device__ __forceinline__ float pack_value(const float* __restrict__ w, int64_t
     const int coe = (G % 6) * 4 + (lane & 3);
     return weight_value(w, tap, cie, coe, Cin_total, ci_off, Cin, Cout, mode, parity);
   }
-  if (idx >= mfma_count) {
-    uint32_t r = (uint32_t)(idx - mfma_count);
-    const int v = (int)(r % NV);
-    r /= NV;
-    const int cil = (int)(r % CK);
-    r /= CK;
-    const int tap = (int)(r % 27);
-    const int cc = (int)(r / 27);
-    const int coutE = mode ? Cin : Cout;
-    return weight_value(w, tap, cc * CK + cil, coutE - NV + v, Cin_total, ci_off, Cin, Cout, mode, parity);
-  }
   const int NCG = CK / 8;
   uint32_t r = (uint32_t)idx;
   const int s = (int)(r & 1);
@@ -262,19 +250,16 @@ __device__ __forceinline__ float pack_value(const float* __restrict__ w, int64_t
   const int kq = lane >> 4, j = lane & 15;
   const int cie = cc * CK + cg * 8 + 2 * kq + s;
   const int coe = (nc * NT + nt) * 16 + j;
-  const int coutE = mode ? Cin : Cout;
-  if (coe >= coutE - NV) return 0.f;  // channels owned by the VALU section
   return weight_value(w, tap, cie, coe, Cin_total, ci_off, Cin, Cout, mode, parity);
 }
 
 __global__ void pack_kernel(const float* __restrict__ w, float* __restrict__ packed, int Cin_total, int ci_off, int Cin,
-                            int Cout, int mode, int CK, int ncc, int NT, int nchunks, int parity, int NV,
-                            int64_t mfma_count, int64_t total) {
+                            int Cout, int mode, int CK, int ncc, int NT, int nchunks, int parity, int64_t total) {
   if (NT <= -100 && NT != -400) {  // split layouts: a thread gathers a weight pair once and writes its three pieces
     const int64_t n3 = total / 3;
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n3; i += (int64_t)gridDim.x * blockDim.x) {
       uint32_t pc[3];
-      split_pack_pair(w, i, Cin_total, ci_off, Cin, Cout, mode, ncc, NT, parity, (int)mfma_count, pc);
+      split_pack_pair(w, i, Cin_total, ci_off, Cin, Cout, mode, ncc, NT, parity, nchunks, pc);
       packed[i] = __uint_as_float(pc[0]);
       packed[i + n3] = __uint_as_float(pc[1]);
       packed[i + 2 * n3] = __uint_as_float(pc[2]);
@@ -283,11 +268,12 @@ __global__ void pack_kernel(const float* __restrict__ w, float* __restrict__ pac
   }
   for (int64_t idx = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; idx < total;
        idx += (int64_t)gridDim.x * blockDim.x)
-    packed[idx] = pack_value(w, idx, Cin_total, ci_off, Cin, Cout, mode, CK, ncc, NT, parity, NV, mfma_count);
+    packed[idx] = pack_value(w, idx, Cin_total, ci_off, Cin, Cout, mode, CK, ncc, NT, parity, nchunks);
 }
 
 // one launch for every layer of the network: jobs[j] = {w_off, dst_off, count, cin_total, ci_off, cin, cout, mode, ck,
-// ncc, nt, parity, nv, mfma_count} (int64 each), blockIdx.y = job
+// ncc, nt, parity, reserved, nchunks} (int64 each), blockIdx.y = job.  The 13th field is ignored; the 14th is read by the split
+// layouts only (nt <= -100: their number of co-chunks)
 constexpr int PACK_JOB_FIELDS = 14;
 __global__ void pack_all_kernel(const float* __restrict__ params, float* __restrict__ packed,
                                 const int64_t* __restrict__ jobs) {
@@ -296,20 +282,19 @@ __global__ void pack_all_kernel(const float* __restrict__ params, float* __restr
   float* dst = packed + jb[1];
   const int64_t count = jb[2];
   const int cin_total = (int)jb[3], ci_off = (int)jb[4], cin = (int)jb[5], cout = (int)jb[6], mode = (int)jb[7],
-            ck = (int)jb[8], ncc = (int)jb[9], nt = (int)jb[10], parity = (int)jb[11], nv = (int)jb[12];
-  const int64_t mfma_count = jb[13];
+            ck = (int)jb[8], ncc = (int)jb[9], nt = (int)jb[10], parity = (int)jb[11], nchunks = (int)jb[13];
   if (nt <= -100 && nt != -400) {  // split layouts: a thread gathers a weight pair once and writes its three pieces
     const int64_t n3 = count / 3;
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n3; i += (int64_t)gridDim.x * blockDim.x) {
       uint32_t pc[3];
-      split_pack_pair(w, i, cin_total, ci_off, cin, cout, mode, ncc, nt, parity, (int)mfma_count, pc);
+      split_pack_pair(w, i, cin_total, ci_off, cin, cout, mode, ncc, nt, parity, nchunks, pc);
       dst[i] = __uint_as_float(pc[0]);
       dst[i + n3] = __uint_as_float(pc[1]);
       dst[i + 2 * n3] = __uint_as_float(pc[2]);
     }
     return;
   }
-  if (nt > 0 && parity >= 0 && parity < 8 && nv == 0) {
+  if (nt > 0 && parity >= 0 && parity < 8) {
     // one parity set of a folded decoder conv in the 27-slot MFMA layout [nc][cc][slot 27][cg][nt][lane][2]: only the 8 slots of
     // the parity's 2x2x2 window (forward orientation: coordinates p .. p + 1 per axis, up_axis_taps) are ever non-zero, the
     // other 19 stay at the zeros the buffer was created with -- 143 of the 259 MB this kernel used to write per step (the
@@ -321,13 +306,13 @@ __global__ void pack_all_kernel(const float* __restrict__ params, float* __restr
       const int t8 = (int)(q & 7);
       const int slot = ((pz + (t8 >> 2)) * 3 + py + ((t8 >> 1) & 1)) * 3 + px + (t8 & 1);
       const int64_t idx = ((q >> 3) * 27 + (mode ? 26 - slot : slot)) * inner + rem;
-      dst[idx] = pack_value(w, idx, cin_total, ci_off, cin, cout, mode, ck, ncc, nt, parity, nv, mfma_count);
+      dst[idx] = pack_value(w, idx, cin_total, ci_off, cin, cout, mode, ck, ncc, nt, parity, nchunks);
     }
     return;
   }
   for (int64_t idx = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; idx < count;
        idx += (int64_t)gridDim.x * blockDim.x)
-    dst[idx] = pack_value(w, idx, cin_total, ci_off, cin, cout, mode, ck, ncc, nt, parity, nv, mfma_count);
+    dst[idx] = pack_value(w, idx, cin_total, ci_off, cin, cout, mode, ck, ncc, nt, parity, nchunks);
 }
 
 // dW of the up-sampled input channels from the 8 per-parity 27-slot gradients: every original tap t belongs to exactly
@@ -440,7 +425,6 @@ struct ConvExt {
                        // the 8 parities, strided INPUT, one accumulated output)
   const float* addend; // mode 1: added before bias/activation, indexed like the output
   int64_t wstride;     // packed-weight stride between parities
-  int64_t valu_off;    // offset of the VALU weight section inside one packed weight set
 };
 
 __host__ __device__ inline uint32_t up_tapmask(int p, bool flipped) {
@@ -458,7 +442,7 @@ __host__ __device__ inline uint32_t up_tapmask(int p, bool flipped) {
   return m;
 }
 
-template <int CK, int NT, int MT, bool KSPLIT, int NV, bool RELU = false>
+template <int CK, int NT, int MT, bool KSPLIT, bool RELU = false>
 __global__ __launch_bounds__(256, 2) void conv3d_fwd_kernel(const float* __restrict__ in, const float* __restrict__ wp,
                                                             const float* __restrict__ bias, float* __restrict__ out,
                                                             int D0, int D1, int D2, int Cin, int Cout, int ncc,
@@ -468,8 +452,6 @@ __global__ __launch_bounds__(256, 2) void conv3d_fwd_kernel(const float* __restr
   constexpr int CKP = CK + 4;
   constexpr int NCG = CK / 8;
   constexpr int C4 = CK / 4;
-  const int dbg = act >> 8;  // diagnostic mask (synthsr_conv3d_set_option 1): 1 no B loads, 2 no A reads, 4 no staging, 8 no stores
-  act &= 0xff;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   // XCD-aware tile order: workgroup b runs on XCD b%8 (observed dispatch order, speed only); give every XCD a
   // contiguous range of tiles so that neighbouring tiles (shared halos) hit the same L2.  Bijective for any grid.
@@ -491,14 +473,6 @@ __global__ __launch_bounds__(256, 2) void conv3d_fwd_kernel(const float* __restr
   for (int m = 0; m < MT; ++m)
 #pragma unroll
     for (int n = 0; n < NT; ++n) acc[m][n] = (f32x4){0.f, 0.f, 0.f, 0.f};
-
-  // vector-ALU share (NV > 0): lane l owns voxel (z = wave, y = l>>4, x = l&15) of the tile and accumulates the last
-  // NV output channels with v_fma, weights from SGPRs (VALU section of the packed buffer), in the shadow of the MFMAs
-  static_assert(NV == 0 || (MT == 4 && !KSPLIT && CK == 24), "VALU share needs the 4x4x16 tile");
-  float accv[NV > 0 ? NV : 1];
-#pragma unroll
-  for (int v = 0; v < (NV > 0 ? NV : 1); ++v) accv[v] = 0.f;
-  const int vbase = ((wave * FH1 + (lane >> 4)) * FH2 + (lane & 15)) * CKP;
 
   const int li = lane & 15, kq = lane >> 4;
   int a_base[MT];
@@ -526,7 +500,7 @@ __global__ __launch_bounds__(256, 2) void conv3d_fwd_kernel(const float* __restr
     // ---- stage the halo tile of this channel chunk (zero padding outside the volume / channel range).
     // Branch-free: out-of-range elements load from a clamped (valid) address and are zeroed by a select, so all
     // global loads are issued back to back before the first LDS store and their latencies overlap.
-    if (!(dbg & 4)) {
+    {
       constexpr int NIT = (FHV * C4 + 255) / 256;
       constexpr int SB = (NT >= 5 && CK == 24) ? (NIT + 1) / 2 : NIT;  // batch size (register budget)
 #pragma unroll
@@ -567,7 +541,6 @@ __global__ __launch_bounds__(256, 2) void conv3d_fwd_kernel(const float* __restr
     __syncthreads();
 
     const float* wc = wl + (size_t)cc * 27 * NCG * NT * 128 + (size_t)par * ext.wstride;
-    const float* wvc = wp + ext.valu_off + (size_t)par * ext.wstride + (size_t)cc * 27 * CK * (NV > 0 ? NV : 1);
     // Software pipeline, pinned with sched_barrier so that hipcc cannot sink the prefetches next to their uses:
     //   B fragments of the next active tap are requested at the top of a tap (one L2 round trip hidden behind
     //   16*NCG*NT MFMAs), A fragments of step (t,g)+1 are read from LDS before the MFMAs of step (t,g).
@@ -580,20 +553,15 @@ __global__ __launch_bounds__(256, 2) void conv3d_fwd_kernel(const float* __restr
       for (int n = 0; n < NT; ++n)
         bcur[g][n] = *reinterpret_cast<const float2*>(wc + (size_t)tap * NCG * NT * 128 + (g * NT + n) * 128);
     float2 acur[MT], anext[MT];
-    float4 xcur[2], xnext[2];
     {
       const int o = tap_off(tap);
 #pragma unroll
       for (int m = 0; m < MT; ++m) acur[m] = *reinterpret_cast<const float2*>(&lds[a_base[m] + o]);
-      if constexpr (NV > 0) {
-        xcur[0] = *reinterpret_cast<const float4*>(&lds[vbase + o]);
-        xcur[1] = *reinterpret_cast<const float4*>(&lds[vbase + o + 4]);
-      }
     }
     while (tap < 27) {
       const uint32_t rem = (tap + 1 < 27) ? (tapmask >> (tap + 1)) : 0u;
       const int tn = rem ? tap + 1 + __builtin_ctz(rem) : 27;
-      if (tn < 27 && !(dbg & 1)) {
+      if (tn < 27) {
         const float* wn = wc + (size_t)tn * NCG * NT * 128;
 #pragma unroll
         for (int g = 0; g < NCG; ++g)
@@ -606,22 +574,9 @@ __global__ __launch_bounds__(256, 2) void conv3d_fwd_kernel(const float* __restr
 #pragma unroll
       for (int g = 0; g < NCG; ++g) {
         const int noff = (g + 1 < NCG) ? toff + (g + 1) * 8 : toff_n;
-        if (!(dbg & 2))
 #pragma unroll
-          for (int m = 0; m < MT; ++m) anext[m] = *reinterpret_cast<const float2*>(&lds[a_base[m] + noff]);
-        if constexpr (NV > 0) {
-          xnext[0] = *reinterpret_cast<const float4*>(&lds[vbase + noff]);
-          xnext[1] = *reinterpret_cast<const float4*>(&lds[vbase + noff + 4]);
-        }
+        for (int m = 0; m < MT; ++m) anext[m] = *reinterpret_cast<const float2*>(&lds[a_base[m] + noff]);
         __builtin_amdgcn_sched_barrier(0);
-        if constexpr (NV > 0) {  // 8 ci x NV co v_fma per lane; weights are wave-uniform -> scalar loads
-          const float* wv = wvc + ((size_t)tap * CK + g * 8) * NV;
-          const float xs[8] = {xcur[0].x, xcur[0].y, xcur[0].z, xcur[0].w, xcur[1].x, xcur[1].y, xcur[1].z, xcur[1].w};
-#pragma unroll
-          for (int c = 0; c < 8; ++c)
-#pragma unroll
-            for (int v = 0; v < NV; ++v) accv[v] = fmaf(xs[c], wv[c * NV + v], accv[v]);
-        }
 #pragma unroll
         for (int n = 0; n < NT; ++n)
 #pragma unroll
@@ -632,20 +587,9 @@ __global__ __launch_bounds__(256, 2) void conv3d_fwd_kernel(const float* __restr
 #pragma unroll
           for (int m = 0; m < MT; ++m)
             acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x4f32(acur[m].y, bcur[g][n].y, acc[m][n], 0, 0, 0);
-        if constexpr (NV > 0) {  // interleave: one MFMA, then its share of the packed v_fma (issued in the MFMA's shadow)
-#pragma unroll
-          for (int q = 0; q < 2 * MT * NT; ++q) {
-            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-            __builtin_amdgcn_sched_group_barrier(0x002, (8 * NV / 2) / (2 * MT * NT), 0);
-          }
-        }
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int m = 0; m < MT; ++m) acur[m] = anext[m];
-        if constexpr (NV > 0) {
-          xcur[0] = xnext[0];
-          xcur[1] = xnext[1];
-        }
       }
 #pragma unroll
       for (int g = 0; g < NCG; ++g)
@@ -657,7 +601,7 @@ __global__ __launch_bounds__(256, 2) void conv3d_fwd_kernel(const float* __restr
 
   // ---- epilogue
   const int gz = z0 + wave;
-  if (gz < D0 && !(dbg & 8)) {
+  if (gz < D0) {
 #pragma unroll
     for (int m = 0; m < MT; ++m) {
       const int gy = y0 + m;
@@ -665,7 +609,7 @@ __global__ __launch_bounds__(256, 2) void conv3d_fwd_kernel(const float* __restr
 #pragma unroll
       for (int n = 0; n < NT; ++n) {
         const int co = (nc * NT + n) * 16 + li;
-        if (co >= Cout - NV) continue;
+        if (co >= Cout) continue;
         const float bv = (!KSPLIT && bias) ? bias[co] : 0.f;
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
@@ -685,21 +629,6 @@ __global__ __launch_bounds__(256, 2) void conv3d_fwd_kernel(const float* __restr
             }
           }
         }
-      }
-    }
-  }
-  if constexpr (NV > 0) {  // the lane's own voxel, channels Cout-NV .. Cout-1
-    const int vy = y0 + (lane >> 4), vx = x0 + (lane & 15);
-    if (gz < D0 && vy < D1 && vx < D2 && !(dbg & 8)) {
-      const int os = (ext.mode == 1) ? 2 : 1;
-      const size_t oidx = (((size_t)(gz * os + ((opar >> 2) & 1)) * (D1 * os) + (vy * os + ((opar >> 1) & 1))) * (D2 * os) +
-                           (vx * os + (opar & 1))) * Cout + (Cout - NV);
-#pragma unroll
-      for (int v = 0; v < NV; ++v) {
-        float r = accv[v] + (bias ? bias[Cout - NV + v] : 0.f);
-        if (ext.addend) r += ext.addend[oidx + v];
-        if (act == 1) r = act_f<RELU>(r);
-        out[oidx + v] = r;
       }
     }
   }
@@ -921,8 +850,6 @@ __global__ __launch_bounds__(256, 2) void conv3d_fwd_p4_kernel(const float* __re
   constexpr int CK = 24, MT = 4, Cout = 24;
   constexpr int FT1 = MT, FH1 = MT + 2;
   constexpr int CKP = CK + 4, C4 = CK / 4;
-  const int dbg = act >> 8;  // timing experiments (synthsr_conv3d_set_option 1): 64 no LDS restage, 128 no epilogue
-  act &= 0xff;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int G = gridDim.x;
   const int my_pos = (blockIdx.x & 7) * (G >> 3) + (blockIdx.x >> 3);
@@ -1022,7 +949,6 @@ __global__ __launch_bounds__(256, 2) void conv3d_fwd_p4_kernel(const float* __re
 #pragma unroll
       for (int g = 0; g < 6; ++g) acc[g] = (f32x4){0.f, 0.f, 0.f, 0.f};
     }
-    if (!(dbg & 64)) {
     __syncthreads();
 #pragma unroll
     for (int i = 0; i < NJ; ++i) {
@@ -1033,7 +959,6 @@ __global__ __launch_bounds__(256, 2) void conv3d_fwd_p4_kernel(const float* __re
       }
     }
     __syncthreads();
-    }
 
     // 81 channel-octet steps (tap, qp); weights of step p live in wr[p % 3] and are requested two steps ahead, the
     // activations of quad step s (two per octet) in xq[s & 1], read one step ahead
@@ -1071,7 +996,7 @@ __global__ __launch_bounds__(256, 2) void conv3d_fwd_p4_kernel(const float* __re
       });
     });
 
-    if (cc == ncc - 1 && !(dbg & 128)) {  // epilogue: the lane's voxel, 24 channels = 6 float4
+    if (cc == ncc - 1) {  // epilogue: the lane's voxel, 24 channels = 6 float4
       const int gz = z0 + wave, gy = y0 + vy, gx = x0 + vx;
       if (gz < D0 && gy < D1 && gx < D2) {
         const size_t o = (((size_t)gz * D1 + gy) * D2 + gx) * Cout;
@@ -1901,7 +1826,6 @@ struct WgExt {
   int cin_total;   // row length of dw in input channels
   int ci_off;      // first input channel of this layer part inside dw
   int64_t dwstride;
-  int dbg;         // timing experiments: 8 = skip the flush
   float* dbias;    // optional: += sum over voxels of dout (a constant-1 GEMM row), else nullptr
   int64_t det_stride;  // deterministic mode: dw / dbias point at per-workgroup-column planes, plane blockIdx.x = + det_stride
                        // floats (0 otherwise: every workgroup adds into the one dw); see det_prepare / det_finish
@@ -2320,7 +2244,6 @@ __global__ __launch_bounds__(256, 2) void conv3d_wgrad_lean_kernel(const float* 
   }
 
   // ---- flush: D row = (lane>>4)*4 + reg -> (tap, ci), col = lane&15 -> co
-  if (ext.dbg & 8) return;
   const size_t detoff = (size_t)blockIdx.x * ext.det_stride;  // deterministic mode: this workgroup column's own plane
 #pragma unroll
   for (int m = 0; m < MTW; ++m) {
@@ -2516,7 +2439,6 @@ __global__ __launch_bounds__(256, 2) void conv3d_wgrad_box_kernel(const float* _
       __builtin_amdgcn_sched_barrier(0);
     }
   }
-  if (ext.dbg & 8) return;
   const size_t detoff = (size_t)blockIdx.x * ext.det_stride;  // deterministic mode: this workgroup column's own plane
 #pragma unroll
   for (int m = 0; m < MTW; ++m) {
@@ -2722,7 +2644,7 @@ __global__ __launch_bounds__(256, 2) void conv3d_up_wgrad_p4_kernel(const float*
                                                                     const float* __restrict__ dout,
                                                                     float* __restrict__ dwc, int D0, int D1, int D2,
                                                                     int Cin, int tiles1, int tiles2, int ntiles,
-                                                                    int64_t dwstride, int dbg, int64_t det_stride) {
+                                                                    int64_t dwstride, int64_t det_stride) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   constexpr int CK = 24, MT = 4, Cout = 24;
   constexpr int FT1 = MT, FH1 = MT + 2, CKP = CK + 4, C4 = CK / 4, NQ = 3;
@@ -2876,7 +2798,6 @@ __global__ __launch_bounds__(256, 2) void conv3d_up_wgrad_p4_kernel(const float*
     y0 = ny0;
     x0 = nx0;
   }
-  if (dbg & 8) return;
   // ---- flush, one wave (= one parity) at a time through LDS: its [8 taps][24 ci][24 co] partial is laid out linearly so
   // that every global atomic instruction covers 64 consecutive floats
   dwc += (size_t)blockIdx.x * det_stride;  // deterministic mode: this workgroup column's own plane (0 otherwise)
@@ -2949,21 +2870,13 @@ static SynDeviceState& dev_state() {
 }
 static inline int det_on() { return dev_state().det; }
 
-// ---- plan parameters.  Rounds 1-4 had a process-wide A/B switch behind each of them (synthsr_conv3d_set_option); every one was
-// measured against its alternative (docs/DESIGN_NOTES_r01_r02.md, profiles/r03_*, r04_*) and the library now ships the winners
-// as constants -- a plan is a pure function of (shape, channels, kind, the context's arithmetic, the device's deterministic mode).
-constexpr int PLAN_PERSIST = 1;            // persistent forward kernel on the large levels
-constexpr int PLAN_FORCE_MT = 0;           // (was a diagnostic override of the tile height)
-constexpr int PLAN_HYBRID = 0;             // MFMA + VALU co-execution for Cout % 16 == 8: correct but slower than padding (hipcc
-                                           // serialises the scalar weight loads behind the MFMAs); kept for the record, off
-constexpr int PLAN_DBG = 0;                // (was the ablation mask)
+// ---- plan parameters.  A plan is a pure function of (shape, channels, kind, the context's arithmetic, the device's deterministic
+// mode).  Every kernel choice in the rules below was measured against its alternative (docs/DESIGN_NOTES_r01_r02.md,
+// profiles/r03_*, r04_*) and only the winner is compiled in; git history holds the rest.  What remains to tune are numbers: the two
+// constants here, and three workgroup counts written where they are used -- 768 (plan_fwd: 4-row tiles; dispatch_wgrad: the
+// all-parity 4x4x1 kernel), 512 (plan_fwd: split-K of the 16-wide tiles) and 400 (plan_fwd: split-K of the bricks; parity_split).
 constexpr int PLAN_KS_TARGET = 1024;       // workgroup target of the split-K heuristic
-constexpr int PLAN_BRICK = 1;              // brick tiles (4x4 voxels per MFMA row block) on the small deep levels
-constexpr int PLAN_P4 = 1;                 // 4x4x1-MFMA kernels for the Cout = 24 layers (no padding to 32 columns)
 constexpr int PLAN_SPLIT_MIN_WGS = 200;    // smallest layer (4x4x16 tiles x co-chunks) on the split kernels (20^3 x 192: -25 %)
-constexpr int PLAN_SPLIT_WGRAD_MIN_TILES = 1;  // split weight gradient at every size (20^3 / 10^3: 4-29 % faster than fp32 MFMA)
-constexpr int PLAN_STACK24 = 1;            // stacked weight layout of the plain Cout = 24 split convs (10 instead of 12 MFMAs)
-constexpr int PLAN_PSPLIT = 1;             // parity split of small up-conv data gradients
 
 // ---- the call's context (include/synthsr_hip.h: synthsr_conv_ctx).  Every extern "C" conv entry point opens a CtxScope on the
 // pointer it was handed; the planners below read cfg().  The scope is thread-local and ends with the call: two threads, or two
@@ -3012,11 +2925,11 @@ extern "C" int syn_split_fwd(const float* in, const float* wp, const float* bias
                              int upm, int stacked, int nprod, hipStream_t st);
 
 // does the weight gradient of a plain 3x3x3 conv take the split kernel (conv_split.hip: syn_split_wgrad)?  One place: the
-// dispatcher and the query synthsr_conv3d_wgrad_runs_split (what the benchmarks price a layer against) both ask here
+// dispatcher and the query synthsr_conv3d_wgrad_runs_split (what the benchmarks price a layer against) both ask here.
+// No lower bound on the tile count: at 20^3 / 10^3 the split kernel is still 4-29 % faster than the fp32 MFMA one.
 inline bool wgrad_takes_split(const int s[3], int Cin, int Cout) {
   const int64_t vox = (int64_t)s[0] * s[1] * s[2];
-  return cfg().split && (int64_t)cdiv(s[0], 4) * cdiv(s[1], 4) * cdiv(s[2], 16) >= PLAN_SPLIT_WGRAD_MIN_TILES && (Cin % 8) == 0 && (Cout % 24) == 0 &&
-         vox * Cin * 4 < (1ll << 31) && vox * Cout * 4 < (1ll << 31);
+  return cfg().split && (Cin % 8) == 0 && (Cout % 24) == 0 && vox * Cin * 4 < (1ll << 31) && vox * Cout * 4 < (1ll << 31);
 }
 
 // ... and the weight gradient of the up-sampled channel range of a folded decoder conv (conv_split.hip: syn_split_upwgrad: six
@@ -3028,20 +2941,17 @@ inline bool up_wgrad_takes_split(const int s[3], int Cl, int Cout) {
 }
 
 struct FwdPlan {
-  int nt, mt, ksplit, nchunks, ncc, ck, persist, nv, p4, c2, brick, wn, wm, split, stacked;
+  int nt, mt, ksplit, nchunks, ncc, ck, persist, p4, c2, brick, wn, wm, split, stacked;
   // NT = 0 selects the 4x4x1 weight layout in pack_value, NT = -Cin the first-layer layout, NT = -100 - MT the split layout,
   // NT = -200 - MT / -300 - MT the split layout of a folded conv's parity set (data gradient / forward window);
   // split: 0 no, 1 plain conv, 2 folded data gradient, 3 folded forward
   int pack_nt() const { return stacked ? -400 : split == 3 ? -300 - mt : (split == 2 ? -200 - mt : (split ? -100 - mt : (c2 ? -c2 : (p4 ? 0 : nt)))); }
-  int64_t mfma_count() const {
-    if (split) return nchunks;  // what pack_value needs to decode the split layout
-    return (p4 || c2) ? 0 : (int64_t)nchunks * ncc * 27 * (ck / 8) * nt * 128;
-  }
   int64_t count() const {
     if (stacked) return (int64_t)ncc * 7 * 5 * 64 * 4;  // [cc][step 7][tile 5][lane 64] x 8 bf16
     if (split) return (int64_t)3 * nchunks * ncc * (split >= 2 ? 2 : 7) * mt * 64 * 4;  // floats (= pairs of bf16)
     if (c2) return (int64_t)((27 * c2 * 6 + 15) / 16) * 64;
-    return p4 ? (int64_t)ncc * 27 * 9 * 64 : mfma_count() + (int64_t)ncc * 27 * ck * nv;
+    if (p4) return (int64_t)ncc * 27 * 9 * 64;
+    return (int64_t)nchunks * ncc * 27 * (ck / 8) * nt * 128;  // [nc][cc][tap][cg][nt][lane][2]
   }
 };
 
@@ -3070,9 +2980,10 @@ inline FwdPlan plan_fwd(const int s[3], int Cin, int Cout, int kind = 1) {
       p.nt = mt;
       p.nchunks = nchunks;
       p.ksplit = 1;
-      // the plain Cout = 24 convs (160^3: forward and data gradient): weight pieces stacked along M (conv_split.hip, STK)
-      p.stacked = (plain && Cout == 24 && cfg().arith == 1 && PLAN_STACK24) ? 1 : 0;
-      p.nv = p.persist = p.p4 = p.c2 = p.brick = 0;
+      // the plain Cout = 24 convs (160^3: forward and data gradient): weight pieces stacked along M (conv_split.hip, STK:
+      // 10 instead of 12 MFMAs)
+      p.stacked = (plain && Cout == 24 && cfg().arith == 1) ? 1 : 0;
+      p.persist = p.p4 = p.c2 = p.brick = 0;
       p.wn = p.wm = 1;
       return p;
     }
@@ -3083,32 +2994,26 @@ inline FwdPlan plan_fwd(const int s[3], int Cin, int Cout, int kind = 1) {
   auto wgs = [&](int mt, int nt) { return (int64_t)cdiv(s[0], FT0) * cdiv(s[1], mt) * cdiv(s[2], FT2) * cdiv(ntiles, nt); };
   p.mt = 4;
   int max_nt = MAX_NT;
-  if (wgs(4, std::min(MAX_NT, ntiles)) < 768 || (PLAN_FORCE_MT == 2 && ntiles <= 3) || p.ck == 32) {  // ck 32: 62 KB halo tile
+  if (wgs(4, std::min(MAX_NT, ntiles)) < 768 || p.ck == 32) {  // < 3 workgroups per CU: 2-row tiles; ck 32: 62 KB halo tile
     p.mt = 2;
     max_nt = 3;
   }
   p.nchunks = cdiv(ntiles, max_nt);
   p.nt = cdiv(ntiles, p.nchunks);
   p.ksplit = 1;
-  p.nv = 0;
-  // MFMA + VALU co-execution: the matrix and vector pipes of a SIMD run concurrently, so instead of padding
-  // Cout = 16 a + 8 to 16 (a + 1) MFMA columns (25 % waste at Cout = 24) the last 8 output channels are computed with
-  // v_fma (weights from SGPRs, activations from the same LDS tile) in the shadow of the MFMAs of the first 16 a.
-  if (PLAN_HYBRID && p.ck == 24 && p.mt == 4 && (Cout % 16) == 8 && Cout >= 24 && ntiles <= 5) {
-    p.nv = 8;
-    p.nchunks = 1;
-    p.nt = (Cout - 8) / 16;
-  }
   const bool lt2g = (int64_t)s[0] * s[1] * s[2] * Cin * 4 < (1ll << 31);  // raw buffer addressing (32-bit offsets)
-  p.persist = (p.mt == 4 && p.ck == 24 && p.nt <= 3 && (Cout % 4) == 0 && PLAN_PERSIST && p.nv == 0 && lt2g) ? 1 : 0;
-  // 4x4x1 layouts: plain Cout = 24 layers, and the forward parity convs of a folded decoder conv with Cout = 24
-  p.p4 = (p.persist && (kind == 1 || kind == 2) && Cout == 24 && (Cin % 24) == 0 && PLAN_P4) ? 1 : 0;
-  p.c2 = (plain && Cout == 24 && Cin <= 2 && lt2g && PLAN_P4) ? Cin : 0;  // first layer: 4x4x1 MFMA over K = 27*Cin
+  // the persistent kernel on the large levels
+  p.persist = (p.mt == 4 && p.ck == 24 && p.nt <= 3 && (Cout % 4) == 0 && lt2g) ? 1 : 0;
+  // 4x4x1 layouts (no padding of 24 output channels to 32 MFMA columns): plain Cout = 24 layers, and the forward parity convs
+  // of a folded decoder conv with Cout = 24
+  p.p4 = (p.persist && (kind == 1 || kind == 2) && Cout == 24 && (Cin % 24) == 0) ? 1 : 0;
+  p.c2 = (plain && Cout == 24 && Cin <= 2 && lt2g) ? Cin : 0;  // first layer: 4x4x1 MFMA over K = 27*Cin
   p.brick = 0;
   p.wn = 1;
   p.wm = 1;
-  if (PLAN_BRICK && p.ck == 24 && p.mt == 2 && lt2g && (Cout % 16) == 0 && p.nv == 0 && (s[0] % 4) == 0 &&
-      (s[1] % 4) == 0 && (s[2] % 4) == 0 && (s[2] % 16) != 0) {
+  // brick tiles (4x4 voxels per MFMA row block) on the small deep levels
+  if (p.ck == 24 && p.mt == 2 && lt2g && (Cout % 16) == 0 && (s[0] % 4) == 0 && (s[1] % 4) == 0 && (s[2] % 4) == 0 &&
+      (s[2] % 16) != 0) {
     // output channels: NT n-tiles per wave, WN waves side by side; `nchunks` (= groups of NT n-tiles) is the packing unit
     p.brick = 1;
     p.nt = (ntiles % 3 == 0) ? 3 : ((ntiles % 2 == 0) ? 2 : 1);
@@ -3134,7 +3039,7 @@ inline FwdPlan plan_fwd(const int s[3], int Cin, int Cout, int kind = 1) {
     return p;
   }
   const int64_t w = wgs(p.mt, p.nt);
-  if (w < 512 && p.ncc >= 4 && plain && p.nv == 0) {
+  if (w < 512 && p.ncc >= 4 && plain) {
     int ks = (int)cdiv(PLAN_KS_TARGET, (int)w);
     if (ks > p.ncc / 2) ks = p.ncc / 2;
     if (ks > 8) ks = 8;
@@ -3147,7 +3052,7 @@ inline FwdPlan plan_fwd(const int s[3], int Cin, int Cout, int kind = 1) {
 // spread over.  1 = all eight inside one workgroup (plain stores); more only when the launch would not fill the chip
 // (20^3 / 10^3 levels: 120 workgroups ran at 16-34 % of the MFMA peak), then every workgroup adds its share atomically.
 inline int parity_split(int64_t workgroups, const float* bias, int act, const ConvExt& ext) {
-  if (!PLAN_PSPLIT || det_on() || bias != nullptr || act != 0 || ext.addend != nullptr) return 1;
+  if (det_on() || bias != nullptr || act != 0 || ext.addend != nullptr) return 1;
   int ps = 1;
   while (ps < 8 && workgroups * ps < 400) ps *= 2;
   return ps;
@@ -3160,79 +3065,84 @@ inline bool launch_act(int& act) {
   return relu;
 }
 
-template <int CK, int NT, int MT, bool KS, int NV = 0>
+// The dynamic-LDS limit of a kernel is raised once per kernel and device (common.h: SynOncePerDevice; the device is marked only
+// after the attribute call returned).  The kernel is a template VALUE: every instantiation, RELU or not, has its own flag.
+template <auto Kern>
+void max_dyn_smem(size_t bytes) {
+  static SynOncePerDevice done;
+  if (auto once_ = done.first()) {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(Kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+  }
+}
+// launches Kern, or KernR (its RELU instantiation) when `relu`, with `smem` bytes of dynamic LDS
+template <auto Kern, auto KernR, class... Args>
+void launch_smem(bool relu, dim3 grid, dim3 block, size_t smem, hipStream_t st, Args... args) {
+  if (relu) {
+    max_dyn_smem<KernR>(smem);
+    hipLaunchKernelGGL(KernR, grid, block, smem, st, args...);
+  } else {
+    max_dyn_smem<Kern>(smem);
+    hipLaunchKernelGGL(Kern, grid, block, smem, st, args...);
+  }
+}
+
+// split-K: the workgroups along gridDim.z add the sums of their input-channel chunks with float atomics -- onto zeros, or onto
+// the addend when that already sits in `out`; bias and activation follow in a second kernel.  Before the launch: every refusal
+// comes ahead of the memset, so a call that returns SYNTHSR_EINVAL has touched nothing.
+inline int splitk_begin(float* out, int64_t nout, int act, const ConvExt& ext, hipStream_t st) {
+  if (ext.mode != 0) return SYNTHSR_EINVAL;  // plan_fwd gives ksplit > 1 to plain convs only
+  if (act != 2 && ext.addend && ext.addend != out) return SYNTHSR_EINVAL;
+  if ((act == 2 || !ext.addend) && hipMemsetAsync(out, 0, (size_t)nout * sizeof(float), st) != hipSuccess) return SYNTHSR_ELAUNCH;
+  return SYNTHSR_OK;
+}
+// ... and after it
+inline int splitk_end(float* out, const float* bias, int64_t nout, int Cout, int act, bool relu, const ConvExt& ext,
+                      hipStream_t st) {
+  if (bias == nullptr && act == 0) return SYNTHSR_OK;
+  hipLaunchKernelGGL((relu ? bias_act_kernel<true> : bias_act_kernel<false>), dim3(syn_grid(nout, 256)), dim3(256), 0, st, out,
+                     bias, nout, Cout, act, act == 2 ? ext.addend : nullptr);
+  return hipGetLastError() == hipSuccess ? SYNTHSR_OK : SYNTHSR_ELAUNCH;
+}
+
+template <int CK, int NT, int MT, bool KS>
 int launch_fwd(const float* in, const float* wp, const float* bias, float* out, const int s[3], int Cin, int Cout,
                const FwdPlan& pl, int act, hipStream_t st, const ConvExt& ext) {
   const bool relu = launch_act(act);
   const int tiles0 = cdiv(s[0], FT0), tiles1 = cdiv(s[1], MT), tiles2 = cdiv(s[2], FT2);
   const size_t smem = (size_t)FH0 * (MT + 2) * FH2 * (CK + 4) * sizeof(float);
-  if constexpr (CK == 24 && NT <= 3 && NV == 0) {
+  const int64_t nout = (int64_t)s[0] * s[1] * s[2] * Cout;
+  // the lean kernel (24-channel chunks, <= 3 n-tiles, raw buffer addressing with 32-bit offsets; 27 taps, or the 8 taps of a
+  // parity set) where the tensors admit it, the generic kernel otherwise
+  enum { GENERIC, LEAN27, LEAN8 } kern = GENERIC;
+  if constexpr (CK == 24 && NT <= 3) {
     const int64_t in_bytes = (int64_t)s[0] * s[1] * s[2] * (ext.mode == 2 ? 8 : 1) * Cin * 4;
     const int64_t w_bytes = pl.count() * 4 * (ext.mode ? 8 : 1);
-    if (in_bytes < (1ll << 31) && w_bytes < (1ll << 31) && !(PLAN_DBG & 32)) {
-      const int64_t nout = (int64_t)s[0] * s[1] * s[2] * Cout;
-      if (KS) {  // split-K accumulates with atomics: onto zeros, or onto the addend when it already sits in `out`
-        if (act != 2 && ext.addend && ext.addend != out) return SYNTHSR_EINVAL;
-        if ((act == 2 || !ext.addend) && hipMemsetAsync(out, 0, (size_t)nout * sizeof(float), st) != hipSuccess)
-          return SYNTHSR_ELAUNCH;
-      }
-      int gz = KS ? pl.ksplit : (ext.mode == 1 ? 8 : 1);
-      if (!KS && ext.mode == 2) {  // few tiles (deep levels): the 8 parity convs of the data gradient go to separate
-        gz = parity_split((int64_t)tiles0 * tiles1 * tiles2 * pl.nchunks, bias, act, ext);  // workgroups (atomics)
-        if (gz > 1 && hipMemsetAsync(out, 0, (size_t)nout * sizeof(float), st) != hipSuccess) return SYNTHSR_ELAUNCH;
-      }
-      const dim3 grid(tiles0 * tiles1 * tiles2, pl.nchunks, gz);
-      if (ext.mode == 0) {
-        static SynOncePerDevice done27, done27r;
-        auto k27 = relu ? conv3d_fwd_lean_kernel<NT, MT, KS, 27, true> : conv3d_fwd_lean_kernel<NT, MT, KS, 27>;
-        if (auto once_ = (relu ? done27r : done27).first()) {
-          (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k27), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-        }
-        hipLaunchKernelGGL(k27, grid, dim3(256), smem, st, in, wp, bias, out, s[0], s[1], s[2], Cin, Cout, pl.ncc, tiles1,
-                           tiles2, act, ext);
-      } else {
-        if constexpr (!KS) {
-          static SynOncePerDevice done8, done8r;
-          auto k8 = relu ? conv3d_fwd_lean_kernel<NT, MT, false, 8, true> : conv3d_fwd_lean_kernel<NT, MT, false, 8>;
-          if (auto once_ = (relu ? done8r : done8).first()) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k8), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-          }
-          hipLaunchKernelGGL(k8, grid, dim3(256), smem, st, in, wp, bias, out, s[0], s[1], s[2], Cin, Cout, pl.ncc, tiles1,
-                             tiles2, act, ext);
-        } else {
-          return SYNTHSR_EINVAL;
-        }
-      }
-      if (hipGetLastError() != hipSuccess) return SYNTHSR_ELAUNCH;
-      if (KS && (bias != nullptr || act != 0)) {
-        hipLaunchKernelGGL((relu ? bias_act_kernel<true> : bias_act_kernel<false>), dim3(syn_grid(nout, 256)), dim3(256), 0, st,
-                           out, bias, nout, Cout, act, act == 2 ? ext.addend : nullptr);
-        if (hipGetLastError() != hipSuccess) return SYNTHSR_ELAUNCH;
-      }
-      return SYNTHSR_OK;
+    if (in_bytes < (1ll << 31) && w_bytes < (1ll << 31)) kern = ext.mode == 0 ? LEAN27 : LEAN8;
+  }
+  if (KS) {
+    if (const int rc = splitk_begin(out, nout, act, ext, st)) return rc;
+  }
+  int gz = KS ? pl.ksplit : (ext.mode == 1 ? 8 : 1);
+  if (!KS && kern == LEAN8 && ext.mode == 2) {  // few tiles (deep levels): the 8 parity convs of the data gradient go to separate
+    gz = parity_split((int64_t)tiles0 * tiles1 * tiles2 * pl.nchunks, bias, act, ext);  // workgroups (atomics)
+    if (gz > 1 && hipMemsetAsync(out, 0, (size_t)nout * sizeof(float), st) != hipSuccess) return SYNTHSR_ELAUNCH;
+  }
+  const dim3 grid(tiles0 * tiles1 * tiles2, pl.nchunks, gz);
+  if constexpr (CK == 24 && NT <= 3) {
+    if (kern == LEAN27)
+      launch_smem<conv3d_fwd_lean_kernel<NT, MT, KS, 27>, conv3d_fwd_lean_kernel<NT, MT, KS, 27, true>>(
+          relu, grid, dim3(256), smem, st, in, wp, bias, out, s[0], s[1], s[2], Cin, Cout, pl.ncc, tiles1, tiles2, act, ext);
+    if constexpr (!KS) {  // (split-K never meets a folded mode: splitk_begin)
+      if (kern == LEAN8)
+        launch_smem<conv3d_fwd_lean_kernel<NT, MT, false, 8>, conv3d_fwd_lean_kernel<NT, MT, false, 8, true>>(
+            relu, grid, dim3(256), smem, st, in, wp, bias, out, s[0], s[1], s[2], Cin, Cout, pl.ncc, tiles1, tiles2, act, ext);
     }
   }
-  static SynOncePerDevice attr_done, attr_done_r;
-  auto kern = relu ? conv3d_fwd_kernel<CK, NT, MT, KS, NV, true> : conv3d_fwd_kernel<CK, NT, MT, KS, NV>;
-  if (auto once_ = (relu ? attr_done_r : attr_done).first()) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-  }
-  const int64_t nout = (int64_t)s[0] * s[1] * s[2] * Cout;
-  if (KS) {
-    if (act != 2 && ext.addend && ext.addend != out) return SYNTHSR_EINVAL;
-    if ((act == 2 || !ext.addend) && hipMemsetAsync(out, 0, (size_t)nout * sizeof(float), st) != hipSuccess)
-      return SYNTHSR_ELAUNCH;
-  }
-  const int gz = KS ? pl.ksplit : (ext.mode == 1 ? 8 : 1);
-  hipLaunchKernelGGL(kern, dim3(tiles0 * tiles1 * tiles2, pl.nchunks, gz), dim3(256), smem, st, in, wp, bias, out, s[0],
-                     s[1], s[2], Cin, Cout, pl.ncc, tiles1, tiles2, act | (PLAN_DBG << 8), ext);
+  if (kern == GENERIC)
+    launch_smem<conv3d_fwd_kernel<CK, NT, MT, KS>, conv3d_fwd_kernel<CK, NT, MT, KS, true>>(
+        relu, grid, dim3(256), smem, st, in, wp, bias, out, s[0], s[1], s[2], Cin, Cout, pl.ncc, tiles1, tiles2, act, ext);
   if (hipGetLastError() != hipSuccess) return SYNTHSR_ELAUNCH;
-  if (KS && (bias != nullptr || act != 0)) {
-    hipLaunchKernelGGL((relu ? bias_act_kernel<true> : bias_act_kernel<false>), dim3(syn_grid(nout, 256)), dim3(256), 0, st,
-                       out, bias, nout, Cout, act, act == 2 ? ext.addend : nullptr);
-    if (hipGetLastError() != hipSuccess) return SYNTHSR_ELAUNCH;
-  }
-  return SYNTHSR_OK;
+  return KS ? splitk_end(out, bias, nout, Cout, act, relu, ext, st) : SYNTHSR_OK;
 }
 
 template <int NT>
@@ -3242,17 +3152,13 @@ int launch_fwd_persist(const float* in, const float* wp, const float* bias, floa
   const int tiles0 = cdiv(s[0], FT0), tiles1 = cdiv(s[1], 4), tiles2 = cdiv(s[2], FT2);
   const int ntiles = tiles0 * tiles1 * tiles2;
   const size_t smem = (size_t)FH0 * 6 * FH2 * 28 * sizeof(float);
-  static SynOncePerDevice attr_done, attr_done_r;
-  auto kern = relu ? conv3d_fwd_persist_kernel<NT, true> : conv3d_fwd_persist_kernel<NT>;
-  if (auto once_ = (relu ? attr_done_r : attr_done).first()) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-  }
   int gx = 512 / pl.nchunks;  // 2 workgroups per CU in total
   gx = std::max(8, (gx / 8) * 8);
   const int64_t nitems = (int64_t)ntiles * pl.ncc;
   while (gx > 8 && gx > nitems) gx -= 8;
-  hipLaunchKernelGGL(kern, dim3(gx, pl.nchunks), dim3(256), smem, st, in, wp, bias, out, s[0], s[1], s[2], Cin, Cout,
-                     pl.ncc, tiles1, tiles2, ntiles, act, addend);
+  launch_smem<conv3d_fwd_persist_kernel<NT>, conv3d_fwd_persist_kernel<NT, true>>(
+      relu, dim3(gx, pl.nchunks), dim3(256), smem, st, in, wp, bias, out, s[0], s[1], s[2], Cin, Cout, pl.ncc, tiles1, tiles2,
+      ntiles, act, addend);
   return hipGetLastError() == hipSuccess ? SYNTHSR_OK : SYNTHSR_ELAUNCH;
 }
 
@@ -3262,11 +3168,6 @@ int launch_fwd_p4(const float* in, const float* wp, const float* bias, float* ou
   const int tiles0 = cdiv(s[0], FT0), tiles1 = cdiv(s[1], 4), tiles2 = cdiv(s[2], FT2);
   const int ntiles = tiles0 * tiles1 * tiles2;
   const size_t smem = (size_t)FH0 * 6 * FH2 * 28 * sizeof(float);
-  static SynOncePerDevice attr_done, attr_done_r;
-  auto kern = relu ? conv3d_fwd_p4_kernel<true> : conv3d_fwd_p4_kernel<false>;
-  if (auto once_ = (relu ? attr_done_r : attr_done).first()) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-  }
   int gx = 512;
   while (gx > 8 && gx > ntiles) gx -= 8;
   float* partial = nullptr;
@@ -3274,8 +3175,9 @@ int launch_fwd_p4(const float* in, const float* wp, const float* bias, float* ou
     partial = ctx_scratch((size_t)gx * 48 * sizeof(float));
     if (!partial) return SYNTHSR_EWORKSPACE;
   }
-  hipLaunchKernelGGL(kern, dim3(gx), dim3(256), smem, st, in, wp, bias, out, s[0], s[1], s[2], Cin, pl.ncc,
-                     tiles1, tiles2, ntiles, act | (PLAN_DBG << 8), addend, partial);
+  launch_smem<conv3d_fwd_p4_kernel<false>, conv3d_fwd_p4_kernel<true>>(relu, dim3(gx), dim3(256), smem, st, in, wp, bias, out,
+                                                                       s[0], s[1], s[2], Cin, pl.ncc, tiles1, tiles2, ntiles,
+                                                                       act, addend, partial);
   if (hipGetLastError() != hipSuccess) return SYNTHSR_ELAUNCH;
   if (stats) return synthsr_bn_stats_from_partials(partial, gx, (int64_t)s[0] * s[1] * s[2], 24, stats, st);
   return SYNTHSR_OK;
@@ -3288,11 +3190,8 @@ int launch_fwd_brick(const float* in, const float* wp, const float* bias, float*
   const int tiles0 = cdiv(s[0], 4), tiles1 = cdiv(s[1], 4 * WM), tiles2 = cdiv(s[2], 4);
   const size_t smem = (size_t)6 * (4 * WM + 2) * 6 * 28 * sizeof(float);
   const int64_t nout = (int64_t)s[0] * s[1] * s[2] * Cout;
-  const float* addend = ext.addend;
   if (KS) {
-    if (act != 2 && addend && addend != out) return SYNTHSR_EINVAL;
-    if ((act == 2 || !addend) && hipMemsetAsync(out, 0, (size_t)nout * sizeof(float), st) != hipSuccess)
-      return SYNTHSR_ELAUNCH;
+    if (const int rc = splitk_begin(out, nout, act, ext, st)) return rc;
   }
   int gz = KS ? pl.ksplit : (ext.mode == 1 ? 8 : 1);
   if (!KS && ext.mode == 2) {
@@ -3304,22 +3203,13 @@ int launch_fwd_brick(const float* in, const float* wp, const float* bias, float*
     auto k27 = relu ? conv3d_fwd_brick_kernel<NT, WM, WN, KS, 27, true> : conv3d_fwd_brick_kernel<NT, WM, WN, KS, 27>;
     hipLaunchKernelGGL(k27, grid, dim3(64 * WM * WN), smem, st, in, wp, bias, out, s[0], s[1], s[2], Cin, Cout, pl.ncc, tiles1,
                        tiles2, act, ext);
-  } else {
-    if constexpr (!KS) {
-      auto k8 = relu ? conv3d_fwd_brick_kernel<NT, WM, WN, false, 8, true> : conv3d_fwd_brick_kernel<NT, WM, WN, false, 8>;
-      hipLaunchKernelGGL(k8, grid, dim3(64 * WM * WN), smem, st, in, wp, bias, out, s[0], s[1], s[2], Cin, Cout, pl.ncc, tiles1,
-                         tiles2, act, ext);
-    } else {
-      return SYNTHSR_EINVAL;
-    }
+  } else if constexpr (!KS) {  // (split-K never meets a folded mode: splitk_begin)
+    auto k8 = relu ? conv3d_fwd_brick_kernel<NT, WM, WN, false, 8, true> : conv3d_fwd_brick_kernel<NT, WM, WN, false, 8>;
+    hipLaunchKernelGGL(k8, grid, dim3(64 * WM * WN), smem, st, in, wp, bias, out, s[0], s[1], s[2], Cin, Cout, pl.ncc, tiles1,
+                       tiles2, act, ext);
   }
   if (hipGetLastError() != hipSuccess) return SYNTHSR_ELAUNCH;
-  if (KS && (bias != nullptr || act != 0)) {
-    hipLaunchKernelGGL((relu ? bias_act_kernel<true> : bias_act_kernel<false>), dim3(syn_grid(nout, 256)), dim3(256), 0, st, out,
-                       bias, nout, Cout, act, act == 2 ? addend : nullptr);
-    if (hipGetLastError() != hipSuccess) return SYNTHSR_ELAUNCH;
-  }
-  return SYNTHSR_OK;
+  return KS ? splitk_end(out, bias, nout, Cout, act, relu, ext, st) : SYNTHSR_OK;
 }
 
 template <int NT, int WM, int WN>
@@ -3359,15 +3249,11 @@ int launch_up_fwd_p4(const float* in, const float* wp, const float* bias, float*
   const int tiles0 = cdiv(s[0], FT0), tiles1 = cdiv(s[1], 4), tiles2 = cdiv(s[2], FT2);
   const int ntiles = tiles0 * tiles1 * tiles2;
   const size_t smem = (size_t)FH0 * 6 * FH2 * 28 * sizeof(float);
-  static SynOncePerDevice attr_done, attr_done_r;
-  auto kern = relu ? conv3d_up_fwd_p4_kernel<true> : conv3d_up_fwd_p4_kernel<false>;
-  if (auto once_ = (relu ? attr_done_r : attr_done).first()) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-  }
   int gx = 512;
   while (gx > 8 && gx > ntiles) gx -= 8;
-  hipLaunchKernelGGL(kern, dim3(gx), dim3(256), smem, st, in, wp, bias, out, s[0], s[1], s[2], Cin,
-                     pl.ncc, tiles1, tiles2, ntiles, act, wstride, addend);
+  launch_smem<conv3d_up_fwd_p4_kernel<false>, conv3d_up_fwd_p4_kernel<true>>(relu, dim3(gx), dim3(256), smem, st, in, wp, bias,
+                                                                             out, s[0], s[1], s[2], Cin, pl.ncc, tiles1, tiles2,
+                                                                             ntiles, act, wstride, addend);
   return hipGetLastError() == hipSuccess ? SYNTHSR_OK : SYNTHSR_ELAUNCH;
 }
 
@@ -3390,9 +3276,6 @@ int dispatch_fwd2(const float* in, const float* wp, const float* bias, float* ou
     return launch_fwd_p4(in, wp, bias, out, s, Cin, pl, act, st, ext.addend);
   }
   if (pl.mt == 4) {
-    if constexpr (CK == 24 && NT <= 4) {
-      if (pl.nv == 8) return launch_fwd<CK, NT, 4, false, 8>(in, wp, bias, out, s, Cin, Cout, pl, act, st, ext);
-    }
     if constexpr (CK == 24 && NT <= 3) {
       if (pl.persist && ext.mode == 0) return launch_fwd_persist<NT>(in, wp, bias, out, s, Cin, Cout, pl, act, st, ext.addend);
     }
@@ -3417,6 +3300,20 @@ int dispatch_fwd(const float* in, const float* wp, const float* bias, float* out
     case 6: return dispatch_fwd2<CK, 6>(in, wp, bias, out, s, Cin, Cout, pl, act, st, ext);
   }
   return SYNTHSR_EINVAL;
+}
+
+// the fp32-MFMA launch of a planned (non-split) layer, by the plan's chunk width
+int dispatch_fwd_ck(const FwdPlan& pl, const float* in, const float* wp, const float* bias, float* out, const int s[3], int Cin,
+                    int Cout, int act, synthsr_stream_t stream, const ConvExt& ext) {
+  const hipStream_t st = (hipStream_t)stream;
+  if (pl.ck == 24) return dispatch_fwd<24>(in, wp, bias, out, s, Cin, Cout, pl, act, st, ext);
+  if (pl.ck == 32) return dispatch_fwd<32>(in, wp, bias, out, s, Cin, Cout, pl, act, st, ext);
+  return dispatch_fwd<8>(in, wp, bias, out, s, Cin, Cout, pl, act, st, ext);
+}
+
+// what every conv entry point asks of its arguments: its three tensors, a shape of positive extents, positive channel counts
+inline bool conv_args_ok(const void* a, const void* b, const void* c, const int shape[3], int Cin, int Cout) {
+  return a && b && c && shape && Cin >= 1 && Cout >= 1 && shape[0] >= 1 && shape[1] >= 1 && shape[2] >= 1;
 }
 
 // ---- deterministic weight gradients: private planes + ordered reduction ------------------------------------------------
@@ -3479,7 +3376,7 @@ int launch_wgrad(const float* in, const float* dout, float* dw, const int s[3], 
   const int ncc = cdiv(Cin, CK), nco = cdiv(Cout, NT * 16);
   const int ymul = (NTAPS == 8) ? 8 : MS;
   // 512 workgroups in total = the 2 per CU that fit: every extra workgroup only adds a 27*CK*Cout atomic flush
-  int gx = (PLAN_FORCE_MT > 8 ? PLAN_FORCE_MT : 512) / (ncc * nco * ymul);
+  int gx = 512 / (ncc * nco * ymul);
   if (gx < 1) gx = 1;
   if (gx > ntiles) gx = ntiles;
   const size_t smem = ((size_t)(CK + 1) * WVPX + (size_t)NT * 16 * WVPD) * sizeof(float);
@@ -3489,7 +3386,7 @@ int launch_wgrad(const float* in, const float* dout, float* dw, const int s[3], 
     if constexpr (NTAPS == 27) {
       // small deep levels: box tiles that divide the volume exactly (4x4x8 for x = 40, 4x4x4 for x = 20)
       const bool div4 = (s[0] % 4) == 0 && (s[1] % 4) == 0 && (s[2] % 4) == 0 && (s[2] % 16) != 0;
-      if (PLAN_BRICK && div4 && (Cout % 4) == 0 && xbytes < (1ll << 31) && dbytes < (1ll << 31) && !(PLAN_DBG & 16)) {
+      if (div4 && (Cout % 4) == 0 && xbytes < (1ll << 31) && dbytes < (1ll << 31)) {
         const bool x8 = (s[2] % 8) == 0;
         const int tx = x8 ? 8 : 4;
         const int bt0 = s[0] / 4, bt1 = s[1] / 4, bt2 = s[2] / tx;
@@ -3513,13 +3410,9 @@ int launch_wgrad(const float* in, const float* dout, float* dw, const int s[3], 
         return syn_det_finish(&det, st);
       }
     }
-    if ((Cout % 4) == 0 && xbytes < (1ll << 31) && dbytes < (1ll << 31) && !(PLAN_DBG & 16)) {
-      static SynOncePerDevice lean_attr_done;
-      auto lkern = conv3d_wgrad_lean_kernel<NT, MS, NTAPS>;
-      if (auto once_ = lean_attr_done.first()) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(lkern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)smem);
-      }
+    if ((Cout % 4) == 0 && xbytes < (1ll << 31) && dbytes < (1ll << 31)) {
+      constexpr auto lkern = conv3d_wgrad_lean_kernel<NT, MS, NTAPS>;
+      max_dyn_smem<lkern>(smem);
       if (const int rc_ = syn_det_prepare(&det, &dw, &ext.dbias, dw_elems, Cout, gx, st)) return rc_;
       ext.det_stride = det.stride;
       hipLaunchKernelGGL(lkern, dim3(gx, ncc * ymul, nco), dim3(256), smem, st, in, dout, dw, s[0], s[1], s[2], Cin, Cout,
@@ -3528,11 +3421,8 @@ int launch_wgrad(const float* in, const float* dout, float* dw, const int s[3], 
       return syn_det_finish(&det, st);
     }
   }
-  static SynOncePerDevice attr_done;
-  auto kern = conv3d_wgrad_kernel<CK, NT, MS, NTAPS>;
-  if (auto once_ = attr_done.first()) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-  }
+  constexpr auto kern = conv3d_wgrad_kernel<CK, NT, MS, NTAPS>;
+  max_dyn_smem<kern>(smem);
   // planes first: a call that returns SYNTHSR_EWORKSPACE has launched NOTHING (the caller repeats it -- a column sum already
   // added to dbias would be counted twice; tests/test_wgrad_scratch_gpu.py: test_too_small_planes_*)
   float* no_dbias = nullptr;
@@ -3561,7 +3451,7 @@ int launch_wgrad(const float* in, const float* dout, float* dw, const int s[3], 
 __global__ __launch_bounds__(256, 2) void conv3d_wgrad_p4_kernel(const float* __restrict__ in,
                                                                  const float* __restrict__ dout, float* __restrict__ dw,
                                                                  int D0, int D1, int D2, int Cin, int tiles1, int tiles2,
-                                                                 int ntiles, int cin_total, int ci_off, int dbg,
+                                                                 int ntiles, int cin_total, int ci_off,
                                                                  float* __restrict__ dbias, int64_t det_stride) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   constexpr int CK = 24, MT = 4, Cout = 24;
@@ -3723,7 +3613,6 @@ __global__ __launch_bounds__(256, 2) void conv3d_wgrad_p4_kernel(const float* __
     y0 = ny0;
     x0 = nx0;
   }
-  if (dbg & 8) return;
   // ---- flush through LDS: the 648 x 24 partial of this workgroup is laid out like the dW chunk ([tap][ci][co]), so that
   // every atomic instruction covers 64 consecutive floats (per-lane rows would issue 64 cache-line requests each)
   __syncthreads();
@@ -3748,7 +3637,7 @@ int launch_wgrad_c2(const float* in, const float* dout, float* dw, float* dbias,
                     const WgExt& ext) {
   const int tiles0 = cdiv(s[0], FT0), tiles1 = cdiv(s[1], 4), tiles2 = cdiv(s[2], FT2);
   const int ntiles = tiles0 * tiles1 * tiles2;
-  int gx = PLAN_FORCE_MT > 8 ? PLAN_FORCE_MT : 2048;  // 8 per CU: per-tile work is short, latency is hidden by occupancy
+  int gx = 2048;  // 8 per CU: per-tile work is short, latency is hidden by occupancy
   while (gx > 8 && gx > ntiles) gx -= 8;
   float* partial = ctx_scratch((size_t)gx * 1536 * sizeof(float));
   if (!partial) return SYNTHSR_EWORKSPACE;
@@ -3777,27 +3666,22 @@ int dispatch_wgrad(const float* in, const float* dout, float* dw, const int shap
     const int64_t vox = (int64_t)shape[0] * shape[1] * shape[2];
     const int tiles0 = cdiv(shape[0], FT0), tiles1 = cdiv(shape[1], 4), tiles2 = cdiv(shape[2], FT2);
     const int ntiles = tiles0 * tiles1 * tiles2, ncc = Cin / 24;
-    if (Cout == 24 && (Cin % 24) == 0 && PLAN_P4 && ntiles >= 768 && vox * Cin * 4 < (1ll << 31) &&
-        vox * 8 * Cout * 4 < (1ll << 31) && !(PLAN_DBG & 16)) {
+    if (Cout == 24 && (Cin % 24) == 0 && ntiles >= 768 && vox * Cin * 4 < (1ll << 31) && vox * 8 * Cout * 4 < (1ll << 31)) {
       const size_t smem = (size_t)FH0 * 6 * FH2 * 28 * sizeof(float);
-      static SynOncePerDevice attr_done;
-      if (auto once_ = attr_done.first()) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv3d_up_wgrad_p4_kernel),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-      }
+      max_dyn_smem<conv3d_up_wgrad_p4_kernel>(smem);
       int gx = std::max(8, ((512 / (ncc * 2)) / 8) * 8);  // each workgroup carries 4 of the 8 parities (one per wave)
       while (gx > 8 && gx > ntiles) gx -= 8;
       DetRun det;
       float* no_dbias = nullptr;
       if (const int rc_ = syn_det_prepare(&det, &dw, &no_dbias, 8 * ext.dwstride, Cout, gx, st)) return rc_;
       hipLaunchKernelGGL(conv3d_up_wgrad_p4_kernel, dim3(gx, ncc * 2), dim3(256), smem, st, in, dout, dw, shape[0], shape[1],
-                         shape[2], Cin, tiles1, tiles2, ntiles, ext.dwstride, ext.dbg, det.stride);
+                         shape[2], Cin, tiles1, tiles2, ntiles, ext.dwstride, det.stride);
       if (hipGetLastError() != hipSuccess) return SYNTHSR_ELAUNCH;
       return syn_det_finish(&det, st);
     }
   }
   if constexpr (NTAPS == 27) {
-    if (Cin <= 2 && Cout == 24 && PLAN_P4 && (int64_t)shape[0] * shape[1] * shape[2] * Cout * 4 < (1ll << 31))
+    if (Cin <= 2 && Cout == 24 && (int64_t)shape[0] * shape[1] * shape[2] * Cout * 4 < (1ll << 31))
       return launch_wgrad_c2(in, dout, dw, ext.dbias, shape, Cin, st, ext);
     // fp32 through three bf16 pieces per operand (conv_split.hip): layers with enough 4x4x16 tiles
     if (wgrad_takes_split(shape, Cin, Cout)) {
@@ -3807,23 +3691,18 @@ int dispatch_wgrad(const float* in, const float* dout, float* dw, const int shap
   }
   if constexpr (NTAPS == 27) {
     const int64_t vox = (int64_t)shape[0] * shape[1] * shape[2];
-    if (Cout == 24 && (Cin % 24) == 0 && PLAN_P4 && vox * Cin * 4 < (1ll << 31) && vox * Cout * 4 < (1ll << 31) &&
-        !(PLAN_DBG & 16)) {
+    if (Cout == 24 && (Cin % 24) == 0 && vox * Cin * 4 < (1ll << 31) && vox * Cout * 4 < (1ll << 31)) {
       const int tiles0 = cdiv(shape[0], FT0), tiles1 = cdiv(shape[1], 4), tiles2 = cdiv(shape[2], FT2);
       const int ntiles = tiles0 * tiles1 * tiles2, ncc = Cin / 24;
       const size_t smem = (size_t)FH0 * 6 * FH2 * 28 * sizeof(float);
-      static SynOncePerDevice attr_done;
-      if (auto once_ = attr_done.first()) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv3d_wgrad_p4_kernel),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-      }
+      max_dyn_smem<conv3d_wgrad_p4_kernel>(smem);
       int gx = std::max(8, ((512 / ncc) / 8) * 8);
       while (gx > 8 && gx > ntiles) gx -= 8;
       DetRun det;
       float* dbias = ext.dbias;
       if (const int rc_ = syn_det_prepare(&det, &dw, &dbias, (int64_t)27 * ext.cin_total * Cout, Cout, gx, st)) return rc_;
       hipLaunchKernelGGL(conv3d_wgrad_p4_kernel, dim3(gx, ncc), dim3(256), smem, st, in, dout, dw, shape[0], shape[1],
-                         shape[2], Cin, tiles1, tiles2, ntiles, ext.cin_total, ext.ci_off, ext.dbg, dbias, det.stride);
+                         shape[2], Cin, tiles1, tiles2, ntiles, ext.cin_total, ext.ci_off, dbias, det.stride);
       if (hipGetLastError() != hipSuccess) return SYNTHSR_ELAUNCH;
       return syn_det_finish(&det, st);
     }
@@ -3868,7 +3747,7 @@ int64_t synthsr_conv3d_pack_ex(const synthsr_conv_ctx* ctx, const float* w, floa
   for (int p = 0; p < (up ? 8 : 1); ++p) {
     hipLaunchKernelGGL(pack_kernel, dim3(syn_grid(per, 256)), dim3(256), 0, (hipStream_t)stream, w, packed + p * per,
                        Cin_total, ci_off, Cin, Cout, mode, pl.ck, pl.ncc, pl.pack_nt(), pl.nchunks,
-                       up ? p + (up == 2 ? 8 : 0) : -1, pl.nv, pl.mfma_count(), per);
+                       up ? p + (up == 2 ? 8 : 0) : -1, per);
     if (hipGetLastError() != hipSuccess) return SYNTHSR_ELAUNCH;
   }
   return total;
@@ -3890,7 +3769,7 @@ int synthsr_conv3d_plan(const synthsr_conv_ctx* ctx, const int shape[3], int Cin
   out[3] = pl.nchunks;
   out[4] = pl.mt;
   out[5] = (pl.split == 1 && syn_split_fwd_halves(shape, CinE, pl.nchunks, pl.stacked, cfg().nprod)) ? 2 : pl.ksplit;
-  out[6] = pl.nv;
+  out[6] = 0;  // reserved
   out[7] = pl.count();
   return SYNTHSR_OK;
 }
@@ -3956,17 +3835,12 @@ int synthsr_conv3d_fwd(const synthsr_conv_ctx* ctx, const float* in, const float
                        const int shape[3], int Cin, int Cout, int act, synthsr_stream_t stream) {
   const CtxScope scope(ctx);
   if (!scope.ok) return SYNTHSR_EINVAL;
-  if (!in || !wpacked || !out || !shape || Cin < 1 || Cout < 1 || shape[0] < 1 || shape[1] < 1 || shape[2] < 1 ||
-      (act != 0 && act != 1 && act != 3))
-    return SYNTHSR_EINVAL;
+  if (!conv_args_ok(in, wpacked, out, shape, Cin, Cout) || (act != 0 && act != 1 && act != 3)) return SYNTHSR_EINVAL;
   const FwdPlan pl = plan_fwd(shape, Cin, Cout);
   if (pl.split)
     return syn_split_fwd(in, wpacked, bias, nullptr, out, shape, Cin, Cout, pl.mt, pl.nchunks, act, nullptr, nullptr, 0,
                          pl.stacked, cfg().nprod, (hipStream_t)stream);
-  const ConvExt ext{0, nullptr, 0, pl.mfma_count()};
-  if (pl.ck == 24) return dispatch_fwd<24>(in, wpacked, bias, out, shape, Cin, Cout, pl, act, (hipStream_t)stream, ext);
-  if (pl.ck == 32) return dispatch_fwd<32>(in, wpacked, bias, out, shape, Cin, Cout, pl, act, (hipStream_t)stream, ext);
-  return dispatch_fwd<8>(in, wpacked, bias, out, shape, Cin, Cout, pl, act, (hipStream_t)stream, ext);
+  return dispatch_fwd_ck(pl, in, wpacked, bias, out, shape, Cin, Cout, act, stream, ConvExt{0, nullptr, 0});
 }
 
 int synthsr_conv3d_fwd_add(const synthsr_conv_ctx* ctx, const float* in, const float* wpacked, const float* bias,
@@ -3974,25 +3848,21 @@ int synthsr_conv3d_fwd_add(const synthsr_conv_ctx* ctx, const float* in, const f
                            synthsr_stream_t stream) {
   const CtxScope scope(ctx);
   if (!scope.ok) return SYNTHSR_EINVAL;
-  if (!in || !wpacked || !out || !shape || Cin < 1 || Cout < 1 || shape[0] < 1 || shape[1] < 1 || shape[2] < 1 ||
-      act < 0 || act > 4 || ((act == 2 || act == 4) && (!addend || addend == out)))
+  if (!conv_args_ok(in, wpacked, out, shape, Cin, Cout) || act < 0 || act > 4 ||
+      ((act == 2 || act == 4) && (!addend || addend == out)))
     return SYNTHSR_EINVAL;
   const FwdPlan pl = plan_fwd(shape, Cin, Cout);
   if (pl.split)
     return syn_split_fwd(in, wpacked, bias, addend, out, shape, Cin, Cout, pl.mt, pl.nchunks, act, nullptr, nullptr, 0,
                          pl.stacked, cfg().nprod, (hipStream_t)stream);
-  const ConvExt ext{0, addend, 0, pl.mfma_count()};
-  if (pl.ck == 24) return dispatch_fwd<24>(in, wpacked, bias, out, shape, Cin, Cout, pl, act, (hipStream_t)stream, ext);
-  if (pl.ck == 32) return dispatch_fwd<32>(in, wpacked, bias, out, shape, Cin, Cout, pl, act, (hipStream_t)stream, ext);
-  return dispatch_fwd<8>(in, wpacked, bias, out, shape, Cin, Cout, pl, act, (hipStream_t)stream, ext);
+  return dispatch_fwd_ck(pl, in, wpacked, bias, out, shape, Cin, Cout, act, stream, ConvExt{0, addend, 0});
 }
 
 int synthsr_conv3d_fwd_stats(const synthsr_conv_ctx* ctx, const float* in, const float* wpacked, const float* bias, float* out,
                              const int shape[3], int Cin, int Cout, int act, float* stats, double* ws, synthsr_stream_t stream) {
   const CtxScope scope(ctx);
   if (!scope.ok) return SYNTHSR_EINVAL;
-  if (!in || !wpacked || !out || !shape || !stats || !ws || Cin < 1 || Cout < 1 || shape[0] < 1 || shape[1] < 1 ||
-      shape[2] < 1 || (act != 0 && act != 1 && act != 3))
+  if (!conv_args_ok(in, wpacked, out, shape, Cin, Cout) || !stats || !ws || (act != 0 && act != 1 && act != 3))
     return SYNTHSR_EINVAL;
   const int64_t nvox = (int64_t)shape[0] * shape[1] * shape[2];
   const FwdPlan pl = plan_fwd(shape, Cin, Cout);
@@ -4014,36 +3884,24 @@ int synthsr_conv3d_up_fwd(const synthsr_conv_ctx* ctx, const float* lo, const fl
                           synthsr_stream_t stream) {
   const CtxScope scope(ctx);
   if (!scope.ok) return SYNTHSR_EINVAL;
-  if (!lo || !wpacked8 || !out || !lo_shape || Cl < 1 || Cout < 1 || lo_shape[0] < 1 || lo_shape[1] < 1 ||
-      lo_shape[2] < 1 || (act != 0 && act != 1 && act != 3))
-    return SYNTHSR_EINVAL;
+  if (!conv_args_ok(lo, wpacked8, out, lo_shape, Cl, Cout) || (act != 0 && act != 1 && act != 3)) return SYNTHSR_EINVAL;
   const FwdPlan pl = plan_fwd(lo_shape, Cl, Cout, 2);
   if (pl.split)  // all parities from one converted low-resolution halo (conv_split.hip: conv3d_split_upfwd_kernel)
     return syn_split_upfwd(lo, wpacked8, bias, addend, out, lo_shape, Cl, Cout, pl.mt, act, cfg().nprod, (hipStream_t)stream);
-  const int64_t wstride = pl.count();
-  const ConvExt ext{1, addend, wstride, pl.mfma_count()};
-  if (pl.ck == 24) return dispatch_fwd<24>(lo, wpacked8, bias, out, lo_shape, Cl, Cout, pl, act, (hipStream_t)stream, ext);
-  if (pl.ck == 32) return dispatch_fwd<32>(lo, wpacked8, bias, out, lo_shape, Cl, Cout, pl, act, (hipStream_t)stream, ext);
-  return dispatch_fwd<8>(lo, wpacked8, bias, out, lo_shape, Cl, Cout, pl, act, (hipStream_t)stream, ext);
+  return dispatch_fwd_ck(pl, lo, wpacked8, bias, out, lo_shape, Cl, Cout, act, stream, ConvExt{1, addend, pl.count()});
 }
 
 int synthsr_conv3d_up_dgrad(const synthsr_conv_ctx* ctx, const float* dout, const float* wpacked8, float* dlo,
                             const int lo_shape[3], int Cl, int Cout, synthsr_stream_t stream) {
   const CtxScope scope(ctx);
   if (!scope.ok) return SYNTHSR_EINVAL;
-  if (!dout || !wpacked8 || !dlo || !lo_shape || Cl < 1 || Cout < 1 || lo_shape[0] < 1 || lo_shape[1] < 1 ||
-      lo_shape[2] < 1)
-    return SYNTHSR_EINVAL;
+  if (!conv_args_ok(dout, wpacked8, dlo, lo_shape, Cl, Cout)) return SYNTHSR_EINVAL;
   // effective conv: input channels = Cout (of the forward layer), output channels = Cl
   const FwdPlan pl = plan_fwd(lo_shape, Cout, Cl, 0);
   if (pl.split)  // the 8 parities as K chunks of one split-arithmetic launch (conv_split.hip, UPM 2)
     return syn_split_fwd(dout, wpacked8, nullptr, nullptr, dlo, lo_shape, Cout, Cl, pl.mt, pl.nchunks, 0, nullptr, nullptr, 2, 0,
                          cfg().nprod, (hipStream_t)stream);
-  const int64_t wstride = pl.count();
-  const ConvExt ext{2, nullptr, wstride, pl.mfma_count()};
-  if (pl.ck == 24) return dispatch_fwd<24>(dout, wpacked8, nullptr, dlo, lo_shape, Cout, Cl, pl, 0, (hipStream_t)stream, ext);
-  if (pl.ck == 32) return dispatch_fwd<32>(dout, wpacked8, nullptr, dlo, lo_shape, Cout, Cl, pl, 0, (hipStream_t)stream, ext);
-  return dispatch_fwd<8>(dout, wpacked8, nullptr, dlo, lo_shape, Cout, Cl, pl, 0, (hipStream_t)stream, ext);
+  return dispatch_fwd_ck(pl, dout, wpacked8, nullptr, dlo, lo_shape, Cout, Cl, 0, stream, ConvExt{2, nullptr, pl.count()});
 }
 
 
@@ -4126,10 +3984,8 @@ int synthsr_conv3d_wgrad_bias(const synthsr_conv_ctx* ctx, const float* in, cons
                               const int shape[3], int Cin_total, int ci_off, int Cin, int Cout, synthsr_stream_t stream) {
   const CtxScope scope(ctx);
   if (!scope.ok) return SYNTHSR_EINVAL;
-  if (!in || !dout || !dw || !shape || Cin < 1 || Cout < 1 || ci_off < 0 || ci_off + Cin > Cin_total || shape[0] < 1 ||
-      shape[1] < 1 || shape[2] < 1)
-    return SYNTHSR_EINVAL;
-  const WgExt ext{0, Cin_total, ci_off, 0, PLAN_DBG, dbias};
+  if (!conv_args_ok(in, dout, dw, shape, Cin, Cout) || ci_off < 0 || ci_off + Cin > Cin_total) return SYNTHSR_EINVAL;
+  const WgExt ext{0, Cin_total, ci_off, 0, dbias};
   return dispatch_wgrad<27>(in, dout, dw, shape, Cin, Cout, (hipStream_t)stream, ext);
 }
 
@@ -4147,9 +4003,8 @@ int synthsr_conv3d_up_wgrad(const synthsr_conv_ctx* ctx, const float* lo, const 
                             int Cl, int Cout, synthsr_stream_t stream) {
   const CtxScope scope(ctx);
   if (!scope.ok) return SYNTHSR_EINVAL;
-  if (!lo || !dout || !dwc || !lo_shape || Cl < 1 || Cout < 1 || lo_shape[0] < 1 || lo_shape[1] < 1 || lo_shape[2] < 1)
-    return SYNTHSR_EINVAL;
-  const WgExt ext{1, Cl, 0, (int64_t)27 * Cl * Cout, PLAN_DBG, nullptr};
+  if (!conv_args_ok(lo, dout, dwc, lo_shape, Cl, Cout)) return SYNTHSR_EINVAL;
+  const WgExt ext{1, Cl, 0, (int64_t)27 * Cl * Cout, nullptr};
   return dispatch_wgrad<8>(lo, dout, dwc, lo_shape, Cl, Cout, (hipStream_t)stream, ext);
 }
 

@@ -21,8 +21,8 @@ Branches the list of the routes names that the public entry points cannot reach 
    so dispatch_fwd2's `pl.c2 && ext.mode != 0` refusal is dead code behind the public API;
  * a stacked split layout with MT != 2: plan_fwd stacks only Cout == 24, whose two 16-column tiles always give MT = 2, and
    syn_split_fwd is not exported;
- * split-K under a folded mode (launch_fwd / launch_fwd_brick return SYNTHSR_EINVAL after their memset): plan_fwd gives
-   ksplit > 1 to plain convs only.
+ * split-K under a folded mode (splitk_begin, the prologue launch_fwd and launch_fwd_brick share, returns SYNTHSR_EINVAL before
+   it touches the output): plan_fwd gives ksplit > 1 to plain convs only.
 
 Measured on an MI355X (worst element / rms error of the reference rms; forward with bias and the data gradient; bf16 rows include
 the one bf16 rounding of the result).  The file takes 12 s there.
