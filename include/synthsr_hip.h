@@ -611,6 +611,23 @@ int synthsr_seg_dice_bwd(const float* probs, const int32_t* seg, int64_t nvox, i
                          const int32_t* cls_idx, const int32_t* cls_gt, int K, const float* sums, float scale, float* dbn,
                          synthsr_stream_t stream);
 
+/* --- training a softmax-headed segmentation U-Net with the soft-Dice loss (fp32) -----------------------------------------
+ * x [nvox][C]: the last feature map (16-byte aligned), stats / gamma / beta / eps: the last BatchNorm; w [C][N], b [N]: the
+ * head; seg [nvox]: the raw label map (label VALUES); lut [lut_n]: label value -> head channel or -1.  A voxel whose label
+ * is outside [0, lut_n) or maps to -1 has an all-zero ground truth (DiceLoss with enable_checks=False on an incomplete label
+ * map; the convention of the seg_dice kernels above).  C <= 64 with C % 4 == 0, N <= 64: anything else returns
+ * SYNTHSR_EINVAL before any launch.
+ * fwd: probs[v][n] = softmax_n(bn(x[v]) . w + b) written; sums[n] += 2 gt p, sums[N + n] += gt^2 + p^2 (sums [2N] zeroed by
+ *      the caller); every voxel is read once.  loss = mean_n(1 - (sums[n] + 1e-7) / (sums[N + n] + 1e-7)).
+ * bwd: gradient of scale * loss: dbn [nvox][C] (w.r.t. the BatchNorm output) written; dw [C][N] and db [N] accumulated. */
+int synthsr_seg_head_dice_fwd(const float* x, int64_t nvox, int C, const float* stats, const float* gamma, const float* beta,
+                              float eps, const float* w, const float* b, int N, const int32_t* seg, const int32_t* lut,
+                              int lut_n, float* probs, float* sums, synthsr_stream_t stream);
+int synthsr_seg_head_dice_bwd(const float* probs, const int32_t* seg, const int32_t* lut, int lut_n, const float* x,
+                              int64_t nvox, int C, int N, const float* stats, const float* gamma, const float* beta, float eps,
+                              const float* w, const float* sums, float scale, float* dbn, float* dw, float* db,
+                              synthsr_stream_t stream);
+
 /* keras.optimizers.Adam (Keras 2.3.1; SynthSR/training.py:444): lr_t = lr*sqrt(1-b2^t)/(1-b1^t),
  * p -= lr_t*m/(sqrt(v)+eps).  lr already includes the 1/(1+decay*iter) factor. */
 int synthsr_adam_step(float* p, const float* g, float* m, float* v, int64_t n, float lr_t, float beta1,

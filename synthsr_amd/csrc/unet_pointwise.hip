@@ -1435,6 +1435,315 @@ __global__ __launch_bounds__(256) void seg_dice_bwd_kernel(const float* __restri
   }
 }
 
+// ------------------------------------------------------------------ trainable softmax head + soft Dice (fp32)
+// Training a segmentation U-Net: head, softmax and DiceLoss (ext/lab2im/layers.py:1343-1376, enable_checks=False) fused, the
+// ground truth taken from the raw label map through a lookup table (label value -> head channel, -1 / outside the table = no
+// class: an all-zero one-hot row).  Both kernels work on tiles of 64 voxels per workgroup, 16 per wave, and form their small
+// matrix products on the fp32 matrix instruction (v_mfma_f32_16x16x4_f32: lane l holds A[l & 15][l >> 4] and B[l >> 4][l & 15];
+// result register r of lane l is D[4 (l >> 4) + r][l & 15]).  Each wave stages its 16 voxels in its own LDS rows, whose stride
+// is (16 blocks + 4) floats = 4 x an odd number: the 16 rows x 4 consecutive columns of an A operand read down the voxel axis
+// fall on 64 different banks, and the 4 rows x 16 consecutive columns of an operand read along a row on at most two per bank.
+constexpr int SHD_TILE = 64;  // voxels per workgroup iteration (4 waves x 16)
+typedef float shd_f32x4 __attribute__((ext_vector_type(4)));
+inline int shd_stride(int blocks16) { return blocks16 * 16 + 4; }
+
+// head channel of a label value, or -1
+__device__ __forceinline__ int shd_class(int lab, const int32_t* __restrict__ lut, int lut_n, int N) {
+  const int k = (lab >= 0 && lab < lut_n) ? lut[lab] : -1;
+  return (k >= 0 && k < N) ? k : -1;
+}
+
+// probs[v][n] = softmax_n(bn(x[v]) . w + b), sums[n] += 2 gt p, sums[N + n] += gt^2 + p^2: one pass, every voxel read once.
+// Dynamic LDS (floats): wl [C][SW] | xs [4][16][SX] | scale, shift [64 + 64] | bias [64] | class [64] | red [4][128] | st [128]
+__global__ __launch_bounds__(256) void seg_head_dice_fwd_kernel(const float* __restrict__ x, int64_t nvox, int C,
+                                                                const float* __restrict__ stats,
+                                                                const float* __restrict__ gamma,
+                                                                const float* __restrict__ beta, float eps,
+                                                                const float* __restrict__ W, const float* __restrict__ b, int N,
+                                                                const int32_t* __restrict__ seg,
+                                                                const int32_t* __restrict__ lut, int lut_n,
+                                                                float* __restrict__ probs, float* __restrict__ sums, int SX,
+                                                                int SW) {
+  extern __shared__ float smem[];
+  const int NB = (N + 15) >> 4, C4 = C >> 2;
+  float* wl = smem;
+  float* xs = wl + C * SW;
+  float* ssc = xs + SHD_TILE * SX;
+  float* ssh = ssc + 64;
+  float* sb = ssh + 64;
+  int* scls = reinterpret_cast<int*>(sb + 64);
+  float* red = sb + 128;
+  float* st = red + 4 * 128;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, col = lane & 15, quad = lane >> 4;
+  for (int i = tid; i < C * SW; i += 256) {
+    const int c = i / SW, n = i - c * SW;
+    wl[i] = n < N ? W[c * N + n] : 0.f;
+  }
+  for (int i = tid; i < C; i += 256) bn_coeff(stats, gamma, beta, eps, C, i, ssc[i], ssh[i]);
+  for (int i = tid; i < 64; i += 256) sb[i] = i < N ? b[i] : 0.f;
+  __syncthreads();
+  float* xw = xs + wave * 16 * SX;
+  int* cw = scls + wave * 16;
+  float top[4] = {0.f, 0.f, 0.f, 0.f}, bot[4] = {0.f, 0.f, 0.f, 0.f};
+  for (int64_t base = (int64_t)blockIdx.x * SHD_TILE; base < nvox; base += (int64_t)gridDim.x * SHD_TILE) {
+    const int64_t v0 = base + wave * 16;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {  // BatchNorm output of the wave's 16 voxels (rows past the volume: zeros)
+      const int i = lane + 64 * j;
+      if (i < 16 * C4) {
+        const int r = i / C4, c = (i - r * C4) * 4;
+        float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (v0 + r < nvox) {
+          const float4 a = ld4(x + (v0 + r) * C + c);
+          o = make_float4(fmaf(a.x, ssc[c], ssh[c]), fmaf(a.y, ssc[c + 1], ssh[c + 1]), fmaf(a.z, ssc[c + 2], ssh[c + 2]),
+                          fmaf(a.w, ssc[c + 3], ssh[c + 3]));
+        }
+        *reinterpret_cast<float4*>(xw + r * SX + c) = o;
+      }
+    }
+    if (lane < 16) cw[lane] = v0 + lane < nvox ? shd_class(seg[v0 + lane], lut, lut_n, N) : -1;
+    __syncthreads();
+    shd_f32x4 acc[4];
+#pragma unroll
+    for (int nb = 0; nb < 4; ++nb) acc[nb] = shd_f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int c0 = 0; c0 < C; c0 += 4) {  // logits [16 voxels][16 classes] per class block, K = channels
+      const float a = xw[col * SX + c0 + quad];
+#pragma unroll
+      for (int nb = 0; nb < 4; ++nb)
+        if (nb < NB) acc[nb] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, wl[(c0 + quad) * SW + nb * 16 + col], acc[nb], 0, 0, 0);
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {  // voxel 4 quad + r of the wave: its classes sit in the 16 lanes of the quad x NB registers
+      float lg[4], mx = -INFINITY;
+#pragma unroll
+      for (int nb = 0; nb < 4; ++nb) {
+        const int n = nb * 16 + col;
+        lg[nb] = (nb < NB && n < N) ? acc[nb][r] + sb[n] : -INFINITY;
+        mx = fmaxf(mx, lg[nb]);
+      }
+#pragma unroll
+      for (int o = 1; o < 16; o <<= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
+      float den = 0.f;
+#pragma unroll
+      for (int nb = 0; nb < 4; ++nb) {
+        lg[nb] = (nb < NB && nb * 16 + col < N) ? expf(lg[nb] - mx) : 0.f;
+        den += lg[nb];
+      }
+#pragma unroll
+      for (int o = 1; o < 16; o <<= 1) den += __shfl_xor(den, o, 64);
+      const float inv = 1.f / den;
+      const int64_t v = v0 + 4 * quad + r;
+      const int k = cw[4 * quad + r];
+#pragma unroll
+      for (int nb = 0; nb < 4; ++nb) {
+        const int n = nb * 16 + col;
+        if (nb < NB && n < N && v < nvox) {
+          const float p = lg[nb] * inv;
+          probs[v * N + n] = p;
+          const float gt = k == n ? 1.f : 0.f;
+          top[nb] += 2.f * gt * p;
+          bot[nb] += gt + p * p;
+        }
+      }
+    }
+  }
+  // the four quads of a wave, then the four waves in order, then ONE flush per workgroup
+#pragma unroll
+  for (int nb = 0; nb < 4; ++nb) {
+    top[nb] += __shfl_xor(top[nb], 16, 64);
+    top[nb] += __shfl_xor(top[nb], 32, 64);
+    bot[nb] += __shfl_xor(bot[nb], 16, 64);
+    bot[nb] += __shfl_xor(bot[nb], 32, 64);
+    if (lane < 16) {
+      red[wave * 128 + nb * 16 + lane] = top[nb];
+      red[wave * 128 + 64 + nb * 16 + lane] = bot[nb];
+    }
+  }
+  __syncthreads();
+  for (int i = tid; i < 2 * N; i += 256) {
+    const int k = i < N ? i : 64 + i - N;
+    st[i] = (red[k] + red[128 + k]) + (red[256 + k] + red[384 + k]);
+  }
+  __syncthreads();
+  if (syn_det_gather(st, 2 * N))
+    for (int i = tid; i < 2 * N; i += 256) atomicAdd(&sums[i], st[i]);
+  syn_det_gather_end(2 * N);
+}
+
+// Backward of scale * mean_n(1 - (T_n + e) / (B_n + e)) through the softmax, the head and into the last BatchNorm's output:
+//   g_n = -(scale / N) (2 gt_n (B_n + e) - 2 p_n (T_n + e)) / (B_n + e)^2,   dlogit_n = p_n (g_n - sum_m g_m p_m)
+//   dbn[v][c] = sum_n dlogit_n w[c][n]   (written);   A[n][c] = sum_v dlogit_n xhat[v][c],  Bs[n] = sum_v dlogit_n
+//   dw[c][n] += gamma[c] A[n][c] + beta[c] Bs[n],  db[n] += Bs[n]            (the algebra of head_multi_bwd_wide_kernel)
+// A wave keeps dlogit [16][SN] and xhat [16][SX] of its 16 voxels in LDS and forms dbn (K = classes) and A (K = voxels, the
+// accumulators live in registers for the whole sweep) on the matrix instruction.
+// Dynamic LDS (floats): wl [16 NB][SW] (w transposed, zero padded) | dl [4][16][SN] | xs [4][16][SX] | ga, gb [64 + 64] |
+// mean, rstd [64 + 64] | class [64]; the workgroup's partial A [N][C] | Bs [N] is gathered in dl | xs after the sweep.
+__global__ __launch_bounds__(256) void seg_head_dice_bwd_kernel(const float* __restrict__ probs, const int32_t* __restrict__ seg,
+                                                                const int32_t* __restrict__ lut, int lut_n,
+                                                                const float* __restrict__ x, int64_t nvox, int C, int N,
+                                                                const float* __restrict__ stats,
+                                                                const float* __restrict__ gamma,
+                                                                const float* __restrict__ beta, float eps,
+                                                                const float* __restrict__ W, const float* __restrict__ sums,
+                                                                float scale, float* __restrict__ dbn, float* __restrict__ dw,
+                                                                float* __restrict__ db, int SX, int SN, int SW) {
+  extern __shared__ float smem[];
+  const int NB = (N + 15) >> 4, CB = (C + 15) >> 4, C4 = C >> 2;
+  float* wl = smem;
+  float* dl = wl + NB * 16 * SW;
+  float* xs = dl + SHD_TILE * SN;
+  float* sga = xs + SHD_TILE * SX;
+  float* sgb = sga + 64;
+  float* smean = sgb + 64;
+  float* srstd = smean + 64;
+  int* scls = reinterpret_cast<int*>(srstd + 64);
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, col = lane & 15, quad = lane >> 4;
+  for (int i = tid; i < NB * 16 * SW; i += 256) {
+    const int n = i / SW, c = i - n * SW;
+    wl[i] = (n < N && c < C) ? W[c * N + n] : 0.f;
+  }
+  for (int i = tid; i < SHD_TILE * (SN + SX); i += 256) dl[i] = 0.f;  // the padding columns stay zero
+  const float coef = -scale / (float)N;
+  for (int i = tid; i < 64; i += 256) {
+    float ga = 0.f, gb = 0.f;
+    if (i < N) {
+      const float T = sums[i] + 1e-7f, B = sums[N + i] + 1e-7f;
+      ga = coef * 2.f / B;
+      gb = coef * 2.f * T / (B * B);
+    }
+    sga[i] = ga;
+    sgb[i] = gb;
+    if (i < C) {
+      smean[i] = stats[i];
+      srstd[i] = rsqrtf(stats[C + i] + eps);
+    }
+  }
+  __syncthreads();
+  float* dlw = dl + wave * 16 * SN;
+  float* xw = xs + wave * 16 * SX;
+  int* cw = scls + wave * 16;
+  shd_f32x4 accA[4][4];
+#pragma unroll
+  for (int nb = 0; nb < 4; ++nb)
+#pragma unroll
+    for (int cb = 0; cb < 4; ++cb) accA[nb][cb] = shd_f32x4{0.f, 0.f, 0.f, 0.f};
+  float bs = 0.f;
+  const int q64 = 64 / N, r64 = 64 - q64 * N;
+  for (int64_t base = (int64_t)blockIdx.x * SHD_TILE; base < nvox; base += (int64_t)gridDim.x * SHD_TILE) {
+    const int64_t v0 = base + wave * 16;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {  // xhat of the wave's 16 voxels
+      const int i = lane + 64 * j;
+      if (i < 16 * C4) {
+        const int r = i / C4, c = (i - r * C4) * 4;
+        float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (v0 + r < nvox) {
+          const float4 a = ld4(x + (v0 + r) * C + c);
+          o = make_float4((a.x - smean[c]) * srstd[c], (a.y - smean[c + 1]) * srstd[c + 1], (a.z - smean[c + 2]) * srstd[c + 2],
+                          (a.w - smean[c + 3]) * srstd[c + 3]);
+        }
+        *reinterpret_cast<float4*>(xw + r * SX + c) = o;
+      }
+    }
+    {  // their 16 N posteriors: one contiguous run (rows past the volume: zeros, so that their dlogit is zero)
+      int r = lane / N, n = lane - r * N;
+      for (int i = lane; i < 16 * N; i += 64) {
+        dlw[r * SN + n] = v0 + r < nvox ? probs[v0 * N + i] : 0.f;
+        r += q64;
+        n += r64;
+        if (n >= N) {
+          n -= N;
+          ++r;
+        }
+      }
+    }
+    if (lane < 16) cw[lane] = v0 + lane < nvox ? shd_class(seg[v0 + lane], lut, lut_n, N) : -1;
+    __syncthreads();
+    {  // four lanes per voxel: S = sum_n g_n p_n, then dlogit in place
+      const int r = lane >> 2, q = lane & 3, k = cw[r];
+      float S = 0.f;
+      for (int n = q; n < N; n += 4) {
+        const float p = dlw[r * SN + n];
+        const float g = (k == n ? sga[n] : 0.f) - p * sgb[n];
+        S = fmaf(g, p, S);
+      }
+      S += __shfl_xor(S, 1, 64);
+      S += __shfl_xor(S, 2, 64);
+      for (int n = q; n < N; n += 4) {
+        const float p = dlw[r * SN + n];
+        const float g = (k == n ? sga[n] : 0.f) - p * sgb[n];
+        dlw[r * SN + n] = p * (g - S);
+      }
+    }
+    __syncthreads();
+    if (lane < N) {
+      float t = 0.f;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) t += dlw[r * SN + lane];
+      bs += t;
+    }
+    shd_f32x4 accD[4];
+#pragma unroll
+    for (int cb = 0; cb < 4; ++cb) accD[cb] = shd_f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int n0 = 0; n0 < NB * 16; n0 += 4) {  // dbn [16 voxels][16 channels] per channel block, K = classes
+      const float a = dlw[col * SN + n0 + quad];
+#pragma unroll
+      for (int cb = 0; cb < 4; ++cb)
+        if (cb < CB) accD[cb] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, wl[(n0 + quad) * SW + cb * 16 + col], accD[cb], 0, 0, 0);
+    }
+#pragma unroll
+    for (int cb = 0; cb < 4; ++cb) {
+      const int c = cb * 16 + col;
+      if (cb < CB && c < C) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int64_t v = v0 + 4 * quad + r;
+          if (v < nvox) dbn[v * C + c] = accD[cb][r];
+        }
+      }
+    }
+#pragma unroll
+    for (int k0 = 0; k0 < 16; k0 += 4) {  // A [16 classes][16 channels] per block pair, K = the 16 voxels
+      float a[4], bx[4];
+#pragma unroll
+      for (int nb = 0; nb < 4; ++nb) a[nb] = nb < NB ? dlw[(k0 + quad) * SN + nb * 16 + col] : 0.f;
+#pragma unroll
+      for (int cb = 0; cb < 4; ++cb) bx[cb] = cb < CB ? xw[(k0 + quad) * SX + cb * 16 + col] : 0.f;
+#pragma unroll
+      for (int nb = 0; nb < 4; ++nb)
+#pragma unroll
+        for (int cb = 0; cb < 4; ++cb)
+          if (nb < NB && cb < CB) accA[nb][cb] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[nb], bx[cb], accA[nb][cb], 0, 0, 0);
+    }
+  }
+  // the four waves add their A | Bs in wave order into part (over dl | xs), then ONE flush per workgroup
+  __syncthreads();
+  float* part = dl;
+  for (int w = 0; w < 4; ++w) {
+    if (wave == w) {
+#pragma unroll
+      for (int nb = 0; nb < 4; ++nb)
+#pragma unroll
+        for (int cb = 0; cb < 4; ++cb)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const int n = nb * 16 + 4 * quad + r, c = cb * 16 + col;
+            if (nb < NB && cb < CB && n < N && c < C) part[n * C + c] = (w ? part[n * C + c] : 0.f) + accA[nb][cb][r];
+          }
+      if (lane < N) part[N * C + lane] = (w ? part[N * C + lane] : 0.f) + bs;
+    }
+    __syncthreads();
+  }
+  if (syn_det_gather(part, N * C + N)) {
+    for (int i = tid; i < C * N; i += 256) {
+      const int c = i / N, n = i - c * N;
+      atomicAdd(&dw[i], gamma[c] * part[n * C + c] + beta[c] * part[N * C + n]);
+    }
+    if (tid < N) atomicAdd(&db[tid], part[N * C + tid]);
+  }
+  syn_det_gather_end(N * C + N);
+}
+
 // ------------------------------------------------------------------------------------------ Adam (Keras 2.3.1)
 __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                    float* __restrict__ m, float* __restrict__ v, int64_t n, float lr_t,
@@ -2061,6 +2370,40 @@ int synthsr_seg_dice_bwd(const float* probs, const int32_t* seg, int64_t nvox, i
     return SYNTHSR_EINVAL;
   hipLaunchKernelGGL(seg_dice_bwd_kernel, dim3(syn_grid(nvox, 256)), dim3(256), 0, (hipStream_t)stream, probs, seg, nvox, C,
                      N, w, cls_idx, cls_gt, K, sums, scale, dbn);
+  SYN_CHECK_LAUNCH();
+  return SYNTHSR_OK;
+}
+
+// limits of the two kernels below (checked before any launch): C <= 64 in whole channel quads, N <= 64, x 16-byte aligned
+static bool shd_ok(int64_t nvox, int C, int N, int lut_n, const void* x) {
+  return nvox >= 1 && C >= 4 && C <= SEG_MAXC && (C % 4) == 0 && N >= 1 && N <= SEG_MAXN && lut_n >= 1 && ((uintptr_t)x % 16) == 0;
+}
+
+int synthsr_seg_head_dice_fwd(const float* x, int64_t nvox, int C, const float* stats, const float* gamma, const float* beta,
+                              float eps, const float* w, const float* b, int N, const int32_t* seg, const int32_t* lut,
+                              int lut_n, float* probs, float* sums, synthsr_stream_t stream) {
+  if (!x || !stats || !gamma || !beta || !w || !b || !seg || !lut || !probs || !sums || !shd_ok(nvox, C, N, lut_n, x))
+    return SYNTHSR_EINVAL;
+  const int SX = shd_stride((C + 15) / 16), SW = shd_stride((N + 15) / 16);
+  const size_t smem = ((size_t)C * SW + (size_t)SHD_TILE * SX + 4 * 64 + 4 * 128 + 128) * sizeof(float);  // <= 38 KB
+  hipLaunchKernelGGL(seg_head_dice_fwd_kernel, dim3(syn_grid(nvox, SHD_TILE, head_grid())), dim3(256), smem, (hipStream_t)stream,
+                     x, nvox, C, stats, gamma, beta, eps, w, b, N, seg, lut, lut_n, probs, sums, SX, SW);
+  SYN_CHECK_LAUNCH();
+  return SYNTHSR_OK;
+}
+
+int synthsr_seg_head_dice_bwd(const float* probs, const int32_t* seg, const int32_t* lut, int lut_n, const float* x, int64_t nvox,
+                              int C, int N, const float* stats, const float* gamma, const float* beta, float eps, const float* w,
+                              const float* sums, float scale, float* dbn, float* dw, float* db, synthsr_stream_t stream) {
+  if (!probs || !seg || !lut || !x || !stats || !gamma || !beta || !w || !sums || !dbn || !dw || !db ||
+      !shd_ok(nvox, C, N, lut_n, x))
+    return SYNTHSR_EINVAL;
+  const int NB = (N + 15) / 16, CB = (C + 15) / 16;
+  const int SX = shd_stride(CB), SN = shd_stride(NB), SW = shd_stride(CB);
+  // at most 3 x 64 x 68 + 320 floats = 53.5 KB, with the deterministic gather's 8 KB of static LDS inside the 64 KB of a launch
+  const size_t smem = ((size_t)NB * 16 * SW + (size_t)SHD_TILE * (SN + SX) + 5 * 64) * sizeof(float);
+  hipLaunchKernelGGL(seg_head_dice_bwd_kernel, dim3(syn_grid(nvox, SHD_TILE, head_grid())), dim3(256), smem, (hipStream_t)stream,
+                     probs, seg, lut, lut_n, x, nvox, C, N, stats, gamma, beta, eps, w, sums, scale, dbn, dw, db, SX, SN, SW);
   SYN_CHECK_LAUNCH();
   return SYNTHSR_OK;
 }

@@ -817,6 +817,51 @@ def seg_dice_bwd(probs, seg, w, cls_idx, cls_gt, sums, scale, dbn):
     return dbn
 
 
+def _seg_head_dice_args(what, x, w, b, seg, lut, probs):
+    """shared checks of seg_head_dice_fwd / _bwd: float32 activations and head, int32 label map and table, shapes that fit"""
+    if x.dim() != 4:
+        raise ValueError('x should be [d0, d1, d2, C]')
+    C = int(x.shape[-1])
+    nvox = x.numel() // C
+    N = w.numel() // C
+    if w.numel() != C * N or N < 1 or b.numel() != N or seg.numel() != nvox or probs.numel() != nvox * N or lut.numel() < 1:
+        raise ValueError('%s: head [%d, %d] with a bias of %d, a label map of %d and posteriors of %d values do not fit %d voxels'
+                         % (what, C, N, b.numel(), seg.numel(), probs.numel(), nvox))
+    if x.dtype != torch.float32 or w.dtype != torch.float32 or probs.dtype != torch.float32:
+        raise ValueError('%s is fp32 only (x is %s)' % (what, x.dtype))
+    if seg.dtype != torch.int32 or lut.dtype != torch.int32:
+        raise ValueError('%s takes the label map and the lookup table as int32 (got %s, %s)' % (what, seg.dtype, lut.dtype))
+    return C, nvox, N
+
+
+def seg_head_dice_fwd(x, stats, gamma, beta, w, b, seg, lut, probs, sums, eps=BN_EPS):
+    """trainable softmax head + soft Dice, forward: probs [nvox, N] = softmax(bn(x) @ w + b) written and sums [2N] (zeroed
+    here) <- the Dice numerators 2 sum gt p | denominators sum gt^2 + p^2, gt = one-hot of lut[seg] (label values outside
+    the table or mapped to -1: no class).  x [d0,d1,d2,C] with C <= 64, N <= 64.  loss = mean(1 - (top + 1e-7) / (bottom +
+    1e-7))"""
+    C, nvox, N = _seg_head_dice_args('seg_head_dice_fwd', x, w, b, seg, lut, probs)
+    if sums.numel() != 2 * N:
+        raise ValueError('seg_head_dice_fwd: sums should hold 2 N = %d values, holds %d' % (2 * N, sums.numel()))
+    sums.zero_()
+    _lib.check(_L().synthsr_seg_head_dice_fwd(_lib.ptr(x), nvox, C, _lib.ptr(stats), _lib.ptr(gamma), _lib.ptr(beta), eps,
+                                              _lib.ptr(w), _lib.ptr(b), N, _lib.ptr(seg), _lib.ptr(lut), int(lut.numel()),
+                                              _lib.ptr(probs), _lib.ptr(sums), _lib.stream()), 'seg_head_dice_fwd')
+    return probs
+
+
+def seg_head_dice_bwd(probs, seg, lut, x, stats, gamma, beta, w, sums, dbn, dw, db, scale=1.0, eps=BN_EPS):
+    """backward of scale * Dice through softmax and head: dbn [d0,d1,d2,C] (gradient w.r.t. the last BatchNorm's output)
+    written, dw [C, N] and db [N] accumulated; probs / sums as seg_head_dice_fwd left them"""
+    C, nvox, N = _seg_head_dice_args('seg_head_dice_bwd', x, w, db, seg, lut, probs)
+    if sums.numel() != 2 * N or dbn.numel() != x.numel() or dw.numel() != C * N or dbn.dtype != torch.float32:
+        raise ValueError('seg_head_dice_bwd: sums [2 N], dbn like x (float32) and dw [C, N] are needed')
+    _lib.check(_L().synthsr_seg_head_dice_bwd(_lib.ptr(probs), _lib.ptr(seg), _lib.ptr(lut), int(lut.numel()), _lib.ptr(x), nvox,
+                                              C, N, _lib.ptr(stats), _lib.ptr(gamma), _lib.ptr(beta), eps, _lib.ptr(w),
+                                              _lib.ptr(sums), float(scale), _lib.ptr(dbn), _lib.ptr(dw), _lib.ptr(db),
+                                              _lib.stream()), 'seg_head_dice_bwd')
+    return dbn
+
+
 def adam_step(p, g, m, v, lr_t, beta1=0.9, beta2=0.999, eps=1e-7, grad_scale=1.0):
     lib = _L()
     _lib.check(lib.synthsr_adam_step(_lib.ptr(p), _lib.ptr(g), _lib.ptr(m), _lib.ptr(v), p.numel(), float(lr_t),

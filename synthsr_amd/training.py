@@ -211,9 +211,10 @@ class Trainer:
         self._auto_pool_used = used + host.nbytes
         return t
 
-    def step(self, model_inputs=None, draws=None, label_index=None):
-        """one training step; returns the loss as a 1-element device tensor (no host sync)"""
-        gen, net = self.gen, self.net
+    def _generate(self, model_inputs=None, draws=None, label_index=None):
+        """the sample of one step (drawn by the host sampler unless given): (image, target, label map, batch size), device
+        tensors that are valid until the next call"""
+        gen = self.gen
         picks = None
         if model_inputs is None:
             mig = self.bg.model_inputs_generator
@@ -240,6 +241,13 @@ class Trainer:
                 else:
                     image, target, seg = gen.generate(np.asarray(labels)[0, ..., 0], np.asarray(means)[0],
                                                       np.asarray(stds)[0], draws, real_image=real)
+        return image, target, seg, B
+
+    def step(self, model_inputs=None, draws=None, label_index=None):
+        """one training step; returns the loss as a 1-element device tensor (no host sync)"""
+        from . import ops
+        net = self.net
+        image, target, seg, B = self._generate(model_inputs, draws, label_index)
         net.set_batch(B)
         residual, rs, ro = None, 1, 0
         if self.residual is not None:
@@ -369,6 +377,43 @@ def load_checkpoint(path, net, by_name=True, skip=()):
         net.iterations = int(z['optimizer/iterations'])
     elif str(path).lower().endswith(('.h5', '.hdf5')) and not skip:
         restore_keras_optimizer(path, net)
+
+
+def fit_loop(step, net, model_dir, init_epoch, epochs, steps_per_epoch, rank=0, verbose=True):
+    """the epochs of a training run around `step()` (one optimizer step, returns the loss as a 1-element device tensor): the
+    epoch's mean loss to logs/loss.csv and to the TensorBoard event file, `%03d.npz` + `%03d.h5` checkpoints per epoch
+    (rank 0), a non-finite epoch loss raises"""
+    import torch
+    log_path = os.path.join(model_dir, 'logs', 'loss.csv')
+    tb = None
+    if rank == 0:
+        os.makedirs(os.path.dirname(log_path), exist_ok=True)
+        from .tb_events import EventFileWriter
+        tb = EventFileWriter(os.path.dirname(log_path))   # KC.TensorBoard(log_dir=model_dir/logs) (SynthSR/training.py:425-431)
+    gc_settled = False
+    for epoch in range(init_epoch, epochs):
+        t0 = time.time()
+        acc = torch.zeros(1, device=net.device)
+        for _ in range(steps_per_epoch):
+            acc += step()
+            if not gc_settled:
+                settle_host_gc()
+                gc_settled = True
+        mean_loss = float(acc.item()) / steps_per_epoch
+        if not np.isfinite(mean_loss):  # tf.debugging.check_numerics in IdentityLoss (metrics_model.py:228)
+            raise FloatingPointError('Loss not finite')
+        if rank == 0:
+            dt = time.time() - t0
+            if verbose:
+                print('Epoch %d/%d - %.1fs - loss: %.6f - %.2f volumes/s/GPU' % (epoch + 1, epochs, dt, mean_loss,
+                                                                                  steps_per_epoch / dt))
+            with open(log_path, 'a') as f:
+                f.write('%d,%.8f,%.3f\n' % (epoch + 1, mean_loss, dt))
+            tb.add_scalar('loss', mean_loss, epoch)   # Keras logs the epoch's mean loss at step = 0-based epoch index
+            save_checkpoint(os.path.join(model_dir, '%03d.npz' % (epoch + 1)), net)
+            save_checkpoint(os.path.join(model_dir, '%03d.h5' % (epoch + 1)), net)  # SynthSR/training.py:429 file name
+    if tb is not None:
+        tb.close()
 
 
 def training(labels_dir, model_dir, prior_means, prior_stds, path_generation_labels, segmentation_label_list=None,
@@ -527,34 +572,5 @@ def training(labels_dir, model_dir, prior_means, prior_stds, path_generation_lab
     trainer = Trainer(brain_generator, net, lr, lr_decay, work_with_residual_channel, distributed=dist_on,
                       seg_regulariser=seg_reg, regression_metric=regression_metric, loss_cropping=loss_cropping)
 
-    log_path = os.path.join(model_dir, 'logs', 'loss.csv')
-    tb = None
-    if rank == 0:
-        os.makedirs(os.path.dirname(log_path), exist_ok=True)
-        from .tb_events import EventFileWriter
-        tb = EventFileWriter(os.path.dirname(log_path))   # KC.TensorBoard(log_dir=model_dir/logs) (SynthSR/training.py:425-431)
-    gc_settled = False
-    for epoch in range(init_epoch, epochs):
-        t0 = time.time()
-        acc = torch.zeros(1, device=net.device)
-        for _ in range(steps_per_epoch):
-            acc += trainer.step()
-            if not gc_settled:
-                settle_host_gc()
-                gc_settled = True
-        mean_loss = float(acc.item()) / steps_per_epoch
-        if not np.isfinite(mean_loss):  # tf.debugging.check_numerics in IdentityLoss (metrics_model.py:228)
-            raise FloatingPointError('Loss not finite')
-        if rank == 0:
-            dt = time.time() - t0
-            if verbose:
-                print('Epoch %d/%d - %.1fs - loss: %.6f - %.2f volumes/s/GPU' % (epoch + 1, epochs, dt, mean_loss,
-                                                                                  steps_per_epoch / dt))
-            with open(log_path, 'a') as f:
-                f.write('%d,%.8f,%.3f\n' % (epoch + 1, mean_loss, dt))
-            tb.add_scalar('loss', mean_loss, epoch)   # Keras logs the epoch's mean loss at step = 0-based epoch index
-            save_checkpoint(os.path.join(model_dir, '%03d.npz' % (epoch + 1)), net)
-            save_checkpoint(os.path.join(model_dir, '%03d.h5' % (epoch + 1)), net)  # SynthSR/training.py:429 file name
-    if tb is not None:
-        tb.close()
+    fit_loop(trainer.step, net, model_dir, init_epoch, epochs, steps_per_epoch, rank=rank, verbose=verbose)
     return net

@@ -353,7 +353,7 @@ class UNet3D:
         self.repack()
 
     # ------------------------------------------------------------------ buffers
-    _F32_BUFS = ('loss', 'dpred', 'pred', 'loss_unused', 'zero_t', 'probs', 'dwc', 'head_ab')
+    _F32_BUFS = ('loss', 'dpred', 'pred', 'loss_unused', 'zero_t', 'probs', 'dwc', 'head_ab', 'dice_sums')
 
     def buf(self, key, shape):
         """persistent scratch tensor: activations / activation gradients in the network's dtype, the head's outputs,
@@ -694,6 +694,35 @@ class UNet3D:
         """forward + unet_likelihood + L1 (SynthSR/metrics_model.py:102-104). Returns (loss tensor[1], pred|None)"""
         return self.loss(x, target, 'l1', None, residual, res_stride, res_off, want_pred)
 
+    def loss_dice(self, x, seg, lut):
+        """training step of a softmax-headed (segmentation) network: forward in training mode + unet_likelihood + softmax +
+        soft Dice (ext/lab2im/layers.py:1343-1376, enable_checks=False) against the label map `seg` (int32 [d0,d1,d2] label
+        VALUES) in one fused head kernel.  lut (int32, device): label value -> head channel or -1; a voxel whose label is
+        outside the table or maps to -1 has an all-zero ground truth.  Returns the loss as a 1-element device tensor;
+        posteriors, Dice sums and the label map are kept for backward().  fp32, batch 1."""
+        if self.final_pred_activation != 'softmax':
+            raise ValueError('loss_dice() is for softmax heads; use loss() for a linear head')
+        if self.bf16:
+            raise NotImplementedError('the soft-Dice training head is fp32 only (dtype=%r)' % 'bf16')
+        if self.batch != 1:
+            raise NotImplementedError('the soft-Dice training head takes one volume per step (batch = %d)' % self.batch)
+        N = self.nb_labels
+        self.training = True
+        self.frozen_batch_stats = False
+        low, bn = self.forward(x)
+        nvox = low.numel() // low.shape[3]
+        if seg.numel() != nvox:
+            raise ValueError('label map of %d voxels for a prediction of %d' % (seg.numel(), nvox))
+        probs = self.buf('probs', [nvox, N])
+        sums = self.buf('dice_sums', [2 * N])
+        seg = seg.reshape(-1)
+        ops.seg_head_dice_fwd(low, self._stats(bn), self.view(bn['gamma']), self.view(bn['beta']), self.view(self.head['w']),
+                              self.view(self.head['b']), seg, lut, probs, sums)
+        self._dice = (probs, sums, seg, lut)
+        self.loss_buf = self.buf('loss', [1])
+        torch.mean(1.0 - (sums[:N] + 1e-7) / (sums[N:] + 1e-7), 0, keepdim=True, out=self.loss_buf)
+        return self.loss_buf
+
     def predict(self, x):
         """inference forward (moving statistics): x [d0,d1,d2,Cin] -> [d0,d1,d2,K] (K = head channels: one per
         regression target; intensities then spreads for a laplace head)"""
@@ -730,6 +759,7 @@ class UNet3D:
         for backward_input).  batch_stats: BatchNorm normalises with the statistics of x's own activations (a frozen Keras
         network inside a model that is being fitted) instead of the moving averages; nothing is updated either way"""
         assert self.nb_labels > 1
+        self._dice = None   # backward() trains only after loss_dice(); this forward is for backward_input()
         self.frozen_batch_stats = bool(batch_stats)
         if batch_stats:
             # Keras' learning phase: the forward pass gathers the batch statistics (conv epilogues / bn_stats) and the
@@ -798,6 +828,16 @@ class UNet3D:
                 self._frozen_sums = torch.zeros_like(self._zero_sums)
             return self._backward_body(g_last, on_grad_ready)
         G.zero_()
+        if self.final_pred_activation == 'softmax':  # trained with the soft Dice (loss_dice): through softmax and head in one pass
+            if getattr(self, '_dice', None) is None:
+                raise RuntimeError('backward() on a softmax head needs loss_dice() first (after predict_probs() the network '
+                                   'is frozen: backward_input())')
+            probs, sums, seg, lut = self._dice
+            dbn = self.buf('dbn_head', list(low.shape))
+            ops.seg_head_dice_bwd(probs, seg, lut, low, self._stats(bn), self.view(bn['gamma']), self.view(bn['beta']),
+                                  self.view(self.head['w']), sums, dbn, self.view(self.head['w'], G),
+                                  self.view(self.head['b'], G))
+            return self._backward_body(dbn, on_grad_ready)
         # the gradient w.r.t. the last BatchNorm output is rank-1 (dpred[v] * w_head[c]): it is neither stored nor
         # reduced; head_bwd emits that BN's backward sums and the first ELU backward forms it on the fly
         if self.nb_labels > 1:  # K-channel linear head (laplace): the gradient w.r.t. the BN output is written out

@@ -1,0 +1,90 @@
+#!/usr/bin/env python
+"""time of the two soft-Dice head kernels (synthsr_seg_head_dice_fwd / _bwd) at the benchmark size next to their compulsory
+HBM traffic, and of one segmentation training step next to the regression step of the same network, in one process:
+
+    python tools/seg_training_bench.py [--size 160] [--C 24] [--N 33] > profiles/seg_training_kernels.txt"""
+import argparse
+import os
+import sys
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from synthsr_amd import ops  # noqa: E402
+from synthsr_amd.unet import UNet3D  # noqa: E402
+
+HBM = 8e12   # bytes / s (MI355X peak)
+
+
+def timed(fn, warm=3, reps=20):
+    for _ in range(warm):
+        fn()
+    evs = []
+    for _ in range(reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        evs.append((a, b))
+    torch.cuda.synchronize()
+    t = sorted(a.elapsed_time(b) for a, b in evs)
+    return t[len(t) // 2], t[0], t[-1]
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--size', type=int, default=160)
+    ap.add_argument('--C', type=int, default=24)
+    ap.add_argument('--N', type=int, default=33)
+    ap.add_argument('--levels', type=int, default=5)
+    a = ap.parse_args()
+    S, C, N = a.size, a.C, a.N
+    nvox = S ** 3
+    g = torch.Generator().manual_seed(0)
+    x = torch.randn(S, S, S, C, generator=g).cuda()
+    stats = torch.cat([torch.zeros(C), torch.ones(C)]).cuda()
+    gamma, beta = torch.ones(C).cuda(), torch.zeros(C).cuda()
+    w, b = (torch.randn(C, N, generator=g) * .3).cuda(), torch.zeros(N).cuda()
+    lut = torch.arange(N, dtype=torch.int32).cuda()
+    seg = torch.randint(0, N + 3, (nvox,), generator=g, dtype=torch.int32).cuda()
+    probs, sums = torch.empty(nvox, N).cuda(), torch.empty(2 * N).cuda()
+    dbn, dw, db = torch.empty_like(x), torch.zeros(C, N).cuda(), torch.zeros(N).cuda()
+    print('soft-Dice head kernels, %d^3 voxels, C = %d, N = %d, fp32 (median / min / max of 20 launches, HIP events)' % (S, C, N))
+    fwd_bytes = nvox * 4 * (C + 1 + N)           # x + label map read, probs written
+    bwd_bytes = nvox * 4 * (N + 1 + C + C)       # probs + label map + x read, dbn written
+    for name, fn, nbytes in (
+            ('seg_head_dice_fwd', lambda: ops.seg_head_dice_fwd(x, stats, gamma, beta, w, b, seg, lut, probs, sums), fwd_bytes),
+            ('seg_head_dice_bwd', lambda: ops.seg_head_dice_bwd(probs, seg, lut, x, stats, gamma, beta, w, sums, dbn, dw, db),
+             bwd_bytes)):
+        med, lo, hi = timed(fn)
+        floor = nbytes / HBM * 1e3
+        print('%-18s %.3f ms (%.3f .. %.3f)   compulsory %.1f MB = %.3f ms at 8 TB/s   -> %.0f %% of the HBM floor rate'
+              % (name, med, lo, hi, nbytes / 1e6, floor, 100 * floor / med))
+    del x, probs, dbn
+    torch.cuda.empty_cache()
+    kw = dict(feat_mult=2, nb_conv_per_level=2, batch_norm=-1)
+    img = torch.rand(S, S, S, 1, generator=g).cuda()
+    target = torch.rand(nvox, generator=g).cuda()
+    segnet = UNet3D(C, [S, S, S, 1], a.levels, 3, N, final_pred_activation='softmax', **kw)
+    regnet = UNet3D(C, [S, S, S, 1], a.levels, 3, 1, final_pred_activation='linear', **kw)
+
+    def seg_step():
+        segnet.loss_dice(img, seg, lut)
+        segnet.backward()
+        segnet.adam_step(1e-4)
+        segnet.update_moving_stats()
+
+    def reg_step():
+        regnet.loss(img, target, 'l1', fuse_head_bwd=True)
+        regnet.backward()
+        regnet.adam_step(1e-4)
+        regnet.update_moving_stats()
+    print('one training step of UNet3D(%d, %d^3 x 1, %d levels), forward + loss + backward + Adam (median / min / max of 10)' % (C, S, a.levels))
+    for name, fn in (('regression step (1-channel l1 head)', reg_step), ('segmentation step (%d-class soft Dice)' % N, seg_step)):
+        med, lo, hi = timed(fn, warm=3, reps=10)
+        print('%-40s %.2f ms (%.2f .. %.2f)' % (name, med, lo, hi))
+
+
+if __name__ == '__main__':
+    main()
