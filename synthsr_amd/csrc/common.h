@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 #include "../../include/synthsr_hip.h"
 
 #define SYN_CHECK_LAUNCH()                                 \
@@ -167,9 +168,8 @@ __device__ __forceinline__ void syn_det_gather_end(int n) {
     syn_turn_end(&d->chain[SYN_DET_CHAINS - 1], syn_wg_linear(), syn_wg_count());
 }
 
-// A kernel attribute (hipFuncSetAttribute: the dynamic LDS size) is set once per kernel AND DEVICE: a launcher keeps one of these
-// as a function-local static and writes  if (auto once_ = attr_done.first()) { hipFuncSetAttribute(...); }  -- the guard marks the
-// device when the if statement ENDS.
+// A kernel attribute (hipFuncSetAttribute: the dynamic LDS size) is set once per kernel AND DEVICE (max_dyn_smem below keeps one of
+// these per kernel): the guard returned by first() marks the device when the if statement that holds it ENDS.
 // The device's bit is set only AFTER the attribute call returned: a second thread that launches on the same device meanwhile
 // sets the (idempotent, cheap) attribute again instead of launching without it.  Device ids beyond 63 never cache.
 #include <atomic>
@@ -192,6 +192,26 @@ struct SynOncePerDevice {
   };
   Guard first() { return Guard{this, needed()}; }
 };
+// Raises the dynamic-LDS limit of Kern before its launch.  The kernel is a template VALUE: every instantiation, RELU or not, has
+// its own flag.
+template <auto Kern>
+void max_dyn_smem(size_t bytes) {
+  static SynOncePerDevice done;
+  if (auto once_ = done.first()) {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(Kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+  }
+}
+// launches Kern, or KernR (its RELU instantiation) when `relu`, with `smem` bytes of dynamic LDS
+template <auto Kern, auto KernR, class... Args>
+void launch_smem(bool relu, dim3 grid, dim3 block, size_t smem, hipStream_t st, Args... args) {
+  if (relu) {
+    max_dyn_smem<KernR>(smem);
+    hipLaunchKernelGGL(KernR, grid, block, smem, st, args...);
+  } else {
+    max_dyn_smem<Kern>(smem);
+    hipLaunchKernelGGL(Kern, grid, block, smem, st, args...);
+  }
+}
 
 // host side of the deterministic WEIGHT-GRADIENT flush (conv3d.hip: det_prepare / det_finish): private planes per workgroup
 // column + an ordered reduction; shared by the fp32 and the bf16 weight-gradient launchers
@@ -267,6 +287,73 @@ __device__ __forceinline__ void syn_split3(float f0, float f1, uint32_t& p0, uin
   p2 = syn_pack_bf16x2(r0, r1);
 }
 #endif
+
+#ifdef __HIPCC__
+// ---- shared by the conv kernels (conv3d.hip, conv_split.hip, conv_bf16.hip) ---------------------------------------------------
+// compile-time loop: f(std::integral_constant<int, I>) for I in [I, N)
+template <int I, int N, class F>
+__device__ __forceinline__ void sfor(F&& f) {
+  if constexpr (I < N) {
+    f(std::integral_constant<int, I>{});
+    sfor<I + 1, N>(f);
+  }
+}
+
+// ELU(alpha = 1) for the fused fp32 epilogues.  Vector-ALU instructions next to MFMAs are not free on gfx950, so instead of
+// libm's expm1f (~22 instructions) the negative branch is 2^(v log2 e) - 1 through v_exp_f32, switched to a degree-5 Taylor
+// polynomial on (-1/8, 0] where the subtraction would cancel.  |error| < 2e-7 absolute and < 2e-6 relative to expm1
+// (tests/test_unet_gpu.py::test_elu_epilogue_accuracy).  The bf16 kernels round the result and keep a shorter one (elu_bf16_f).
+__device__ __forceinline__ float elu_f(float v) {
+  const float e = __builtin_amdgcn_exp2f(v * 1.44269504088896341f) - 1.f;
+  const float p = v * fmaf(v, fmaf(v, fmaf(v, fmaf(v, 1.f / 120.f, 1.f / 24.f), 1.f / 6.f), 0.5f), 1.f);
+  const float n = v > -0.125f ? p : e;
+  return v > 0.f ? v : n;
+}
+// derivative of ELU expressed through its output y: 1 for y > 0, y + 1 (= e^x) otherwise
+__device__ __forceinline__ float elu_dy(float y) { return y > 0.f ? 1.f : y + 1.f; }
+// ReLU (act 3 / 4, Keras activation='relu'): the fp32 kernels take the activation family as a template parameter RELU and run it
+// under the ELU family's act codes 1 / 2, so the ELU instantiations stay the code they were
+template <bool RELU>
+__device__ __forceinline__ float act_f(float v) {
+  if constexpr (RELU) return fmaxf(v, 0.f);
+  else return elu_f(v);
+}
+// derivative through the output: ReLU'(y) = 1 for y > 0, else 0 (TF ReluGrad)
+template <bool RELU>
+__device__ __forceinline__ float act_dy(float y) {
+  if constexpr (RELU) return y > 0.f ? 1.f : 0.f;
+  else return elu_dy(y);
+}
+
+// ---- the 4x4x16-voxel tiles of the split and the bf16 kernels and their order ------------------------------------------------
+// Tiles are enumerated (z-slab of SLAB_Z tile planes, y, z within the slab, x): neighbours in all three directions are close in
+// the list.  The list is cut into 8 contiguous parts, one per XCD (consecutive workgroup ids are dealt round-robin to the XCDs,
+// each with a private L2), and the workgroups of an XCD walk their part (tile_walk of either file): the ~64 tiles an XCD works on
+// at any time form a compact block, so the halo voxels they share are fetched from HBM once (with the plain z-major order every
+// tile pulled its 2.5x halo through on its own: FETCH ~2.5x the tensor).
+constexpr int TZ = 4, TY = 4, TX = 16, HZ = TZ + 2, HY = TY + 2, HX = TX + 2, HVOX = HZ * HY * HX;
+constexpr int SLAB_Z = 4;
+__device__ __forceinline__ void tile_decode(int p, int tiles0, int tiles1, int tiles2, int& z0, int& y0, int& x0) {
+  const int t12 = tiles1 * tiles2;
+  const int s = p / (SLAB_Z * t12), r = p - s * SLAB_Z * t12;
+  const int sz = min(SLAB_Z, tiles0 - s * SLAB_Z);
+  const int t1 = r / (sz * tiles2), rr = r - t1 * sz * tiles2;
+  const int zz = rr / tiles2, t2 = rr - zz * tiles2;
+  z0 = (s * SLAB_Z + zz) * TZ;
+  y0 = t1 * TY;
+  x0 = t2 * TX;
+}
+#endif
+// Workgroups along x of a launch whose persistent workgroups walk `ntiles` tiles, given `slots` workgroup slots for them (what the
+// CUs hold at once, divided by the grid's y and z): a multiple of 8 (one share per XCD), and never narrower than the tile count
+// where that is possible -- 296 workgroups for 300 tiles made 8 stragglers walk two tiles = twice the kernel's critical path.
+static inline int syn_tile_grid_x(int slots, int ntiles) {
+  int gx = slots / 8 * 8;
+  if (gx < 8) gx = 8;
+  while (gx > 8 && gx - 8 >= ntiles) gx -= 8;
+  if (ntiles < 8) gx = ntiles;
+  return gx;
+}
 
 // Output-channel tiles (of 16) per co-chunk of a plain split conv (conv3d.hip plans and packs with it, conv_split.hip launches
 // with it).  Up to three tiles per workgroup (registers), whole co-chunks.  Round 6: a layer whose units (4x4x16 voxel tiles x

@@ -31,40 +31,8 @@ inline int ck_for(int Cin) { return (Cin % 24 == 0) ? 24 : 8; }
 // chunks re-staged the halo tile four times per tile and ran at 6 % of the MFMA peak)
 inline int ck_for_fwd(int Cin) { return (Cin % 24 == 0) ? 24 : ((Cin % 32 == 0) ? 32 : 8); }
 
-template <int I, int N, class F>
-__device__ __forceinline__ void sfor(F&& f) {  // compile-time loop: f(std::integral_constant<int, I>) for I in [I, N)
-  if constexpr (I < N) {
-    f(std::integral_constant<int, I>{});
-    sfor<I + 1, N>(f);
-  }
-}
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-// ELU(alpha = 1) for the fused epilogues.  Vector-ALU instructions next to MFMAs are not free on gfx950 (see the
-// persistent kernel), so instead of libm's expm1f (~22 instructions) the negative branch is 2^(v log2 e) - 1 through
-// v_exp_f32, switched to a degree-5 Taylor polynomial on (-1/8, 0] where the subtraction would cancel.
-// |error| < 2e-7 absolute and < 2e-6 relative to expm1 (tests/test_unet_gpu.py::test_elu_epilogue_accuracy).
-__device__ __forceinline__ float elu_f(float v) {
-  const float e = __builtin_amdgcn_exp2f(v * 1.44269504088896341f) - 1.f;
-  const float p = v * fmaf(v, fmaf(v, fmaf(v, fmaf(v, 1.f / 120.f, 1.f / 24.f), 1.f / 6.f), 0.5f), 1.f);
-  const float n = v > -0.125f ? p : e;
-  return v > 0.f ? v : n;
-}
-// derivative of ELU expressed through its output y: 1 for y > 0, y + 1 (= e^x) otherwise
-__device__ __forceinline__ float elu_dy(float y) { return y > 0.f ? 1.f : y + 1.f; }
-// ReLU (act 3 / 4, Keras activation='relu'): the forward kernels take the activation family as a template parameter RELU and
-// run it under the ELU family's act codes 1 / 2 (launch_act below), so the ELU instantiations stay the code they were
-template <bool RELU>
-__device__ __forceinline__ float act_f(float v) {
-  if constexpr (RELU) return fmaxf(v, 0.f);
-  else return elu_f(v);
-}
-// derivative through the output: ReLU'(y) = 1 for y > 0, else 0 (TF ReluGrad)
-template <bool RELU>
-__device__ __forceinline__ float act_dy(float y) {
-  if constexpr (RELU) return y > 0.f ? 1.f : 0.f;
-  else return elu_dy(y);
-}
 __device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
 
 // -------------------------------------------------------------------------------------------- pack
@@ -3063,27 +3031,6 @@ inline bool launch_act(int& act) {
   const bool relu = act >= 3;
   if (relu) act -= 2;
   return relu;
-}
-
-// The dynamic-LDS limit of a kernel is raised once per kernel and device (common.h: SynOncePerDevice; the device is marked only
-// after the attribute call returned).  The kernel is a template VALUE: every instantiation, RELU or not, has its own flag.
-template <auto Kern>
-void max_dyn_smem(size_t bytes) {
-  static SynOncePerDevice done;
-  if (auto once_ = done.first()) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(Kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-  }
-}
-// launches Kern, or KernR (its RELU instantiation) when `relu`, with `smem` bytes of dynamic LDS
-template <auto Kern, auto KernR, class... Args>
-void launch_smem(bool relu, dim3 grid, dim3 block, size_t smem, hipStream_t st, Args... args) {
-  if (relu) {
-    max_dyn_smem<KernR>(smem);
-    hipLaunchKernelGGL(KernR, grid, block, smem, st, args...);
-  } else {
-    max_dyn_smem<Kern>(smem);
-    hipLaunchKernelGGL(Kern, grid, block, smem, st, args...);
-  }
 }
 
 // split-K: the workgroups along gridDim.z add the sums of their input-channel chunks with float atomics -- onto zeros, or onto

@@ -45,16 +45,10 @@ typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 typedef uint16_t bf16_t;
 
-constexpr int TZ = 4, TY = 4, TX = 16, HZ = TZ + 2, HY = TY + 2, HX = TX + 2, HVOX = HZ * HY * HX;
 constexpr uint32_t OOB = 0x80000000u;
 
-// ---- tile schedule shared by the forward and the weight-gradient kernel -------------------------------------------------
-// Tiles are enumerated (z-slab of SLAB_Z tile planes, y, z within the slab, x): neighbours in all three directions are
-// close in the list.  The list is cut into 8 contiguous parts, one per XCD (consecutive workgroup ids are dealt round-robin
-// to the XCDs, each with a private L2), and the workgroups of an XCD walk their part with stride G / 8: the ~64 tiles an
-// XCD works on at any time form a compact block, so the halo voxels they share are fetched from HBM once (with the plain
-// z-major order every 4x4x16 tile pulled its 2.5x halo through on its own: FETCH ~2.5x the tensor).
-constexpr int SLAB_Z = 4;
+// ---- tile schedule shared by the forward and the weight-gradient kernel (tile order: common.h) -------------------------------
+// the workgroups of an XCD walk their eighth of the list with stride G / 8 (equal parts, unlike conv_split.hip's tile_walk)
 struct TileWalk {
   int pos, end, stride;
 };
@@ -73,16 +67,6 @@ __device__ __forceinline__ TileWalk tile_walk(int ntiles) {
   }
   return w;
 }
-__device__ __forceinline__ void tile_decode(int p, int tiles0, int tiles1, int tiles2, int& z0, int& y0, int& x0) {
-  const int t12 = tiles1 * tiles2;
-  const int s = p / (SLAB_Z * t12), r = p - s * SLAB_Z * t12;
-  const int sz = min(SLAB_Z, tiles0 - s * SLAB_Z);
-  const int t1 = r / (sz * tiles2), rr = r - t1 * sz * tiles2;
-  const int zz = rr / tiles2, t2 = rr - zz * tiles2;
-  z0 = (s * SLAB_Z + zz) * TZ;
-  y0 = t1 * TY;
-  x0 = t2 * TX;
-}
 
 // LDS row strides (bytes), odd multiples of 16 B so that the 16 lanes of an x-row hit 16 different bank quads.
 // weight gradient: room for CK channels + the constant-1 pad block; forward: no pad needed (24 ch = 48 B = 3 quads)
@@ -90,28 +74,19 @@ __device__ __forceinline__ void tile_decode(int p, int tiles0, int tiles1, int t
 __host__ __device__ constexpr int rowb_for(int ck) { return ck == 8 ? 32 : 96; }
 __host__ __device__ constexpr int rowb_fwd(int ck) { return ck == 8 ? 16 : (ck == 24 ? 48 : 80); }
 
-template <int I, int N, class F>
-__device__ __forceinline__ void sfor(F&& f) {
-  if constexpr (I < N) {
-    f(std::integral_constant<int, I>{});
-    sfor<I + 1, N>(f);
-  }
-}
-
 // ELU(alpha = 1) for a bf16 result: 2^(v log2 e) - 1 through v_exp_f32 has an ABSOLUTE error of ~6e-8 (the subtraction
 // cancels near 0), i.e. below half a bf16 ulp of the result for |v| > 3e-5 and negligible below -- no polynomial branch as
 // in the fp32 kernels: 4 vector-ALU instructions instead of 14 (the epilogue of a 24 -> 24 tile is 32 values per lane)
-__device__ __forceinline__ float elu_f(float v) {
+__device__ __forceinline__ float elu_bf16_f(float v) {
   const float e = __builtin_amdgcn_exp2f(v * 1.44269504088896341f) - 1.f;
   return v > 0.f ? v : e;
 }
-__device__ __forceinline__ float elu_dy(float y) { return y > 0.f ? 1.f : y + 1.f; }
 // act 6 = ReLU(conv + bias + addend), the ReLU twin of act 5: the kernels' RELU instantiation runs it as act 5 with this function,
 // so the ELU instantiation stays the code it was (act 3 / 4 with alpha = 0 are ReLU and ReLU' already)
 template <bool RELU>
 __device__ __forceinline__ float act5_f(float v) {
   if constexpr (RELU) return fmaxf(v, 0.f);
-  else return elu_f(v);
+  else return elu_bf16_f(v);
 }
 
 __device__ __forceinline__ uint32_t f2bf(float f) {  // round to nearest even (finite inputs)
@@ -441,7 +416,7 @@ __global__ __launch_bounds__(256, 2) void conv3d_bf16_fwd_kernel(const FwdArgs a
             for (int i = 0; i < 4; ++i) v[i] = acc[y][mt][i] + bias_r[mt][i];
             if constexpr (ACT == 1) {
 #pragma unroll
-              for (int i = 0; i < 4; ++i) v[i] = elu_f(v[i]);
+              for (int i = 0; i < 4; ++i) v[i] = elu_bf16_f(v[i]);
             } else if constexpr (ACT == 2) {
               const u32x2 b = __builtin_amdgcn_raw_buffer_load_b64(rbelow, (int)off, 0, 0);
               v[0] *= elu_dy(bf2f(b.x & 0xffffu));
@@ -514,7 +489,7 @@ __global__ __launch_bounds__(256, 2) void conv3d_bf16_fwd_kernel(const FwdArgs a
         for (int i = 0; i < 4; ++i) v[i] = acc[y][mt][i] + bias_r[mt][i];
         if (a.act == 1) {
 #pragma unroll
-          for (int i = 0; i < 4; ++i) v[i] = elu_f(v[i]);
+          for (int i = 0; i < 4; ++i) v[i] = elu_bf16_f(v[i]);
         } else if (a.act == 2) {
           const u32x2 b = *reinterpret_cast<const u32x2*>(a.below + vox * Cout + co);
           v[0] *= elu_dy(bf2f(b.x & 0xffffu));
@@ -578,9 +553,7 @@ __global__ __launch_bounds__(256, 2) void conv3d_bf16_fwd_kernel(const FwdArgs a
 
 template <int CK, int MT, bool WLDS>
 int launch_fwd_w(const FwdArgs& a0, int nchunks, hipStream_t st) {
-  int gx = 512;
-  while (gx > 8 && gx - 8 >= a0.ntiles) gx -= 8;  // never narrower than the tile count: a second tile doubles a straggler's time
-  if (a0.ntiles < 8) gx = a0.ntiles;
+  const int gx = syn_tile_grid_x(512, a0.ntiles);
   constexpr int NSTEP = (27 * (CK / 8) + 3) / 4;
   const size_t hbytes = ((size_t)HVOX * rowb_fwd(CK) + 1023) / 1024 * 1024;
   const size_t smem = hbytes + (WLDS ? (size_t)NSTEP * MT * 1024 : 0);
@@ -588,27 +561,18 @@ int launch_fwd_w(const FwdArgs& a0, int nchunks, hipStream_t st) {
   const bool relu = a0.act == 6 || (a0.act == 3 && a0.stats_partial && a0.alpha == 0.f);
   FwdArgs a = a0;
   if (relu) a.act = 5;
-  auto kern = relu ? conv3d_bf16_fwd_kernel<CK, MT, WLDS, 0, true> : conv3d_bf16_fwd_kernel<CK, MT, WLDS>;
-  static SynOncePerDevice attr_done, attr_done_r;
-  if (auto once_ = (relu ? attr_done_r : attr_done).first()) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-  }
-  hipLaunchKernelGGL(kern, dim3(gx, nchunks, a.ksplit), dim3(256), smem, st, a);
+  constexpr auto kern_r = conv3d_bf16_fwd_kernel<CK, MT, WLDS, 0, true>, kern = conv3d_bf16_fwd_kernel<CK, MT, WLDS>;
+  launch_smem<kern, kern_r>(relu, dim3(gx, nchunks, a.ksplit), dim3(256), smem, st, a);
   return hipGetLastError() == hipSuccess ? SYNTHSR_OK : SYNTHSR_ELAUNCH;
 }
 
 // folded variants (UPM 1: gridDim.z = 8 output parities; UPM 2: gridDim.z = K slices over the 8 x ncc_real chunks)
 template <int CK, int MT, int UPM>
 int launch_fwd_up(const FwdArgs& a, int nchunks, hipStream_t st) {
-  int gx = UPM == 1 ? 64 : 512;  // UPM 1: 8 parities x 64 x chunks workgroups
-  while (gx > 8 && gx - 8 >= a.ntiles) gx -= 8;  // never narrower than the tile count: a second tile doubles a straggler's time
-  if (a.ntiles < 8) gx = a.ntiles;
+  const int gx = syn_tile_grid_x(UPM == 1 ? 64 : 512, a.ntiles);  // UPM 1: 8 parities x 64 x chunks workgroups
   const size_t smem = ((size_t)HVOX * rowb_fwd(CK) + 1023) / 1024 * 1024;
-  auto kern = conv3d_bf16_fwd_kernel<CK, MT, false, UPM>;
-  static SynOncePerDevice attr_done;
-  if (auto once_ = attr_done.first()) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-  }
+  constexpr auto kern = conv3d_bf16_fwd_kernel<CK, MT, false, UPM>;
+  max_dyn_smem<kern>(smem);
   hipLaunchKernelGGL(kern, dim3(gx, nchunks, UPM == 1 ? 8 : a.ksplit), dim3(256), smem, st, a);
   return hipGetLastError() == hipSuccess ? SYNTHSR_OK : SYNTHSR_ELAUNCH;
 }
@@ -652,7 +616,7 @@ __global__ void bf16_epilogue_kernel(const float* __restrict__ partial, const fl
     for (int k = 0; k < 4; ++k) v[k] += bias ? bias[c + k] : 0.f;
     if (act == 1) {
 #pragma unroll
-      for (int k = 0; k < 4; ++k) v[k] = elu_f(v[k]);
+      for (int k = 0; k < 4; ++k) v[k] = elu_bf16_f(v[k]);
     } else if (act == 2) {
       const u32x2 b = *reinterpret_cast<const u32x2*>(below + i * 4);
       v[0] *= elu_dy(bf2f(b.x & 0xffffu));
@@ -995,17 +959,10 @@ __global__ __launch_bounds__(512, (NT <= 2 ? 2 : 1)) void conv3d_bf16_wgrad_kern
 template <int CK, int NT, bool UP = false>
 int launch_wgrad(const WgArgs& a0, hipStream_t st) {
   WgArgs a = a0;
-  int gx = 512 / (a.ncc * a.nco * (UP ? 8 : 1));
-  gx = (gx / 8) * 8;
-  if (gx < 8) gx = 8;
-  while (gx > 8 && gx - 8 >= a.ntiles) gx -= 8;  // never narrower than the tile count: a second tile doubles a straggler's time
-  if (a.ntiles < 8) gx = a.ntiles;
+  const int gx = syn_tile_grid_x(512 / (a.ncc * a.nco * (UP ? 8 : 1)), a.ntiles);
   const size_t smem = (size_t)HVOX * rowb_for(CK) + (size_t)TZ * TY * TX * ((NT & 1) ? NT * 32 : NT * 32 + 32);
-  auto kern = conv3d_bf16_wgrad_kernel<CK, NT, UP>;
-  static SynOncePerDevice attr_done;
-  if (auto once_ = attr_done.first()) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-  }
+  constexpr auto kern = conv3d_bf16_wgrad_kernel<CK, NT, UP>;
+  max_dyn_smem<kern>(smem);
   DetRun det;
   if (const int rc_ = syn_det_prepare(&det, &a.dw, &a.dbias, (int64_t)(UP ? 8 : 1) * 27 * a.cin_total * a.Cout, a.Cout, gx, st)) return rc_;
   a.det_stride = det.stride;
@@ -1111,9 +1068,7 @@ int synthsr_conv3d_bf16_fwd_ex(const void* in, const void* wp, const float* bias
   a.partial = nullptr;
   a.ksplit = 1;
   a.ncc_real = pl.ncc;
-  int gx = 512;
-  while (gx > 8 && gx - 8 >= a.ntiles) gx -= 8;  // never narrower than the tile count: a second tile doubles a straggler's time
-  if (a.ntiles < 8) gx = a.ntiles;
+  const int gx = syn_tile_grid_x(512, a.ntiles);
   const int W = 16 * pl.mt;
   hipStream_t st = (hipStream_t)stream;
   // small deep levels (20^3, 10^3): a handful of tiles cannot fill 256 CUs and each workgroup would walk up to 18 channel
@@ -1304,9 +1259,7 @@ int synthsr_conv3d_bf16_up_dgrad(const void* dout, const void* wpacked8, void* d
   a.ncc = 8 * pl.ncc;
   hipStream_t st = (hipStream_t)stream;
   // small deep levels: split the 8 x ncc K chunks over gridDim.z, fp32 partial planes + the split-K epilogue
-  int gx = 512;
-  while (gx > 8 && gx - 8 >= a.ntiles) gx -= 8;  // never narrower than the tile count: a second tile doubles a straggler's time
-  if (a.ntiles < 8) gx = a.ntiles;
+  const int gx = syn_tile_grid_x(512, a.ntiles);
   const int wgs_plain = gx * pl.nchunks;
   const int ks = std::min(a.ncc, (512 + wgs_plain - 1) / std::max(wgs_plain, 1));
   if (wgs_plain < 256 && ks >= 2 && scratch && scratch_floats >= (int64_t)ks * vox * Cl) {

@@ -24,9 +24,6 @@
 #include <type_traits>
 #include <utility>
 
-#ifndef SYN_ABL  // ablation builds of the interleaved forward kernel (tools/split_ablate.sh): 1 no halo loads, 2 no conversion,
-#define SYN_ABL 0  // 4 no LDS image stores, 8 weights loaded once, 16 activation fragments loaded once per chunk, 32 no stores, 64 no MFMAs
-#endif
 #ifdef SYN_SPLIT_TIMING  // per-phase shader-clock stamps of wave 0 of workgroups 0 and 300 (tools/split_phase_timing.py)
 static __device__ long long* g_tm = nullptr;
 extern "C" int synthsr_split_timing_buffer(long long* p) {
@@ -47,14 +44,12 @@ extern "C" int synthsr_split_timing_buffer(long long* p) {
 
 // Arithmetic "split9" (synthsr_conv_ctx.arithmetic = 2): all nine partial products a_i b_j instead of six -- an fp32 product is
 // then reproduced EXACTLY (tests/test_split_arithmetic_cpu.py) at 1.5x the MFMAs; same packed weights, same kernels (template
-// NPROD).  The number of products is an ARGUMENT of the three entry points below (syn_split_fwd / _upfwd / _wgrad, `nprod`); the
-// launch helpers of this file read it from t_nprod, which those entry points set on every call -- no state survives a call.
-static thread_local int t_nprod = 6;
-// Kernel choices that were A/B switches in rounds 3-4 (options 8 and 12 of the former synthsr_conv3d_set_option) and are now
-// fixed at what the measurements kept (profiles/r04_split_fwd_variants.txt, r04_split_wgrad_*_ab.txt, r05_split_wgrad_var24_ab.txt):
-// forward = conversion inside the K loop (fwd2), the LDS-weights kernel (fwd3) where it quantises better; weight gradient = five
-// stacked column tiles for 24 columns, 48-column workgroups where 48 divides Cout with 16 input channels each where 16 divides
-// Cin, all 24 input channels in one workgroup where Cin = Cout = 24.
+// NPROD).  The number of products is an argument (`nprod`) of the entry points at the end of this file and of the launch helpers
+// they call.
+// Kernel choices that the measurements of rounds 3-5 fixed (profiles/r04_split_fwd_variants.txt, r04_split_wgrad_*_ab.txt,
+// r05_split_wgrad_var24_ab.txt): forward = conversion inside the K loop (fwd2), the LDS-weights kernel (fwd3) where it quantises
+// better (split_fwd_route); weight gradient = five stacked column tiles for 24 columns, 48-column workgroups where 48 divides Cout
+// with 16 input channels each where 16 divides Cin, all 24 input channels in one workgroup where Cin = Cout = 24 (syn_split_wgrad).
 
 namespace {
 
@@ -62,14 +57,12 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
-constexpr int TZ = 4, TY = 4, TX = 16, HZ = TZ + 2, HY = TY + 2, HX = TX + 2, HVOX = HZ * HY * HX;
 constexpr uint32_t OOB = 0x80000000u;
 constexpr int PLANE = HVOX * 16;   // one bf16 piece of an 8-channel halo image
 constexpr int BUF = 3 * PLANE;     // the three pieces
 constexpr int NSTEP27 = 7;         // 27 taps, 4 per MFMA (the 28th slot carries zero weights)
-constexpr int SLAB_Z = 4;
 
-// tile schedule: see conv_bf16.hip (tiles enumerated slab by slab, the list cut into 8 contiguous parts, one per XCD)
+// tile schedule: tiles enumerated slab by slab (common.h: tile_decode), the list cut into 8 contiguous parts, one per XCD
 struct TileWalk {
   int pos, end, stride;
 };
@@ -102,31 +95,12 @@ __host__ __device__ inline TileWalk tile_walk_of(int G, int b, int lin0, int nti
 __device__ __forceinline__ TileWalk tile_walk(int ntiles) {
   return tile_walk_of((int)gridDim.x, (int)blockIdx.x, (int)gridDim.x * (int)(blockIdx.y + gridDim.y * blockIdx.z), ntiles);
 }
-__device__ __forceinline__ void tile_decode(int p, int tiles0, int tiles1, int tiles2, int& z0, int& y0, int& x0) {
-  const int t12 = tiles1 * tiles2;
-  const int s = p / (SLAB_Z * t12), r = p - s * SLAB_Z * t12;
-  const int sz = min(SLAB_Z, tiles0 - s * SLAB_Z);
-  const int t1 = r / (sz * tiles2), rr = r - t1 * sz * tiles2;
-  const int zz = rr / tiles2, t2 = rr - zz * tiles2;
-  z0 = (s * SLAB_Z + zz) * TZ;
-  y0 = t1 * TY;
-  x0 = t2 * TX;
-}
-
 // bits h = 0 .. n - 1 set where the coordinate o + h lies outside [0, D) -- the out-of-range mask of one axis of a staged box in
 // closed form (round 6: the n compare / select / or triplets per axis were ~120 scalar instructions per request)
 __device__ __forceinline__ uint32_t syn_oob_bits(int o, int n, int D) {
   const int lo = max(0, -o), hi = min(n - 1, D - 1 - o);
   const uint32_t valid = hi >= lo ? (((2u << hi) - 1u) & ~((1u << lo) - 1u)) : 0u;
   return ((1u << n) - 1u) & ~valid;
-}
-
-template <int I, int N, class F>
-__device__ __forceinline__ void sfor(F&& f) {
-  if constexpr (I < N) {
-    f(std::integral_constant<int, I>{});
-    sfor<I + 1, N>(f);
-  }
 }
 
 // the partial products (weight / first-operand piece a, activation / second-operand piece b) in issue order, smallest first:
@@ -148,26 +122,6 @@ constexpr int split_combo_b(int c, int np) {
     c -= 3;
   }
   return c == 1 ? 2 : ((c == 2 || c == 4) ? 1 : 0);
-}
-
-// ELU(alpha = 1), fp32 accuracy (same function as conv3d.hip: exp2 away from 0, degree-5 Taylor on (-1/8, 0])
-__device__ __forceinline__ float elu_f(float v) {
-  const float e = __builtin_amdgcn_exp2f(v * 1.44269504088896341f) - 1.f;
-  const float p = v * fmaf(v, fmaf(v, fmaf(v, fmaf(v, 1.f / 120.f, 1.f / 24.f), 1.f / 6.f), 0.5f), 1.f);
-  const float n = v > -0.125f ? p : e;
-  return v > 0.f ? v : n;
-}
-__device__ __forceinline__ float elu_dy(float y) { return y > 0.f ? 1.f : y + 1.f; }
-// ReLU family (act 3 / 4, as conv3d.hip): a template parameter of the kernels, so the ELU instantiations stay as they were
-template <bool RELU>
-__device__ __forceinline__ float act_f(float v) {
-  if constexpr (RELU) return fmaxf(v, 0.f);
-  else return elu_f(v);
-}
-template <bool RELU>
-__device__ __forceinline__ float act_dy(float y) {
-  if constexpr (RELU) return y > 0.f ? 1.f : 0.f;
-  else return elu_dy(y);
 }
 
 struct SplitFwdArgs {
@@ -625,11 +579,7 @@ __global__ __launch_bounds__(256 * KS, KS == 1 ? 2 : 1) void conv3d_split_fwd2_k
 #pragma unroll
     for (int i = i0; i < i1; ++i) {
       const uint32_t vo = (pmask[i] & hbad) ? OOB : (uint32_t)(prel[i] + hbase);
-#if SYN_ABL & 1
-      stg[i] = (f32x4){__uint_as_float(vo), 1.f, 2.f, 3.f};
-#else
       stg[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rin, (int)vo, 0, 0));
-#endif
     }
   };
   using P0 = std::integral_constant<int, 0>;
@@ -637,22 +587,12 @@ __global__ __launch_bounds__(256 * KS, KS == 1 ? 2 : 1) void conv3d_split_fwd2_k
   using P6 = std::integral_constant<int, 6>;
   typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
   uint32_t cp[6];  // the piece being converted: three bf16 pairs of its first / second two values
-#if SYN_ABL & 2
-  auto conv_a = [&](int i) { cp[0] = __float_as_uint(stg[i][0]); cp[1] = __float_as_uint(stg[i][1]); cp[2] = cp[0] ^ cp[1]; };
-  auto conv_b = [&](int i) { cp[3] = __float_as_uint(stg[i][2]); cp[4] = __float_as_uint(stg[i][3]); cp[5] = cp[3] ^ cp[4]; };
-#else
   auto conv_a = [&](int i) { syn_split3(stg[i][0], stg[i][1], cp[0], cp[1], cp[2]); };
   auto conv_b = [&](int i) { syn_split3(stg[i][2], stg[i][3], cp[3], cp[4], cp[5]); };
-#endif
   auto conv_c = [&](int i, unsigned char* dst) {
-#if SYN_ABL & 4
-    if (cp[0] == 0x12345u && cp[5] == 0x54321u)  // (never)
-#endif
-    {
     *reinterpret_cast<u32x2*>(dst + plds0 + i * 2048) = (u32x2){cp[0], cp[3]};
     *reinterpret_cast<u32x2*>(dst + PLANE2 + plds0 + i * 2048) = (u32x2){cp[1], cp[4]};
     *reinterpret_cast<u32x2*>(dst + 2 * PLANE2 + plds0 + i * 2048) = (u32x2){cp[2], cp[5]};
-    }
   };
 
   // weight fragments.  Plain layout: piece q at q * piece_stride, fragment (cc, step, mt) at ((cc * NSTEP + step) * MT + mt) * 64;
@@ -683,21 +623,13 @@ __global__ __launch_bounds__(256 * KS, KS == 1 ? 2 : 1) void conv3d_split_fwd2_k
   // Register budget (2 workgroups per CU: 256 VGPRs): ONE set of weight fragments and ONE set of activation fragments; every
   // fragment is re-loaded for the next step right after its last use and then not needed for >= 12 (plain) / 20 (STK) MFMAs
   u32x4 wa[STK ? 1 : 3][STK ? STK_TILES : MT], xb[3][TY];
-  bool wfirst = true;
-  (void)wfirst;
   auto wload = [&](const u32x4* wf, int s, int q) {  // plain: piece q of step s
-#if SYN_ABL & 8
-    if (!wfirst) return;
-#endif
     if constexpr (!STK) {
 #pragma unroll
       for (int mt = 0; mt < MT; ++mt) wa[q][mt] = wf[q * piece_stride + (s * MT + mt) * 64];
     }
   };
   auto wload_t = [&](const u32x4* wf, int s, int tl) {  // STK: row tile tl of step s
-#if SYN_ABL & 8
-    if (!wfirst) return;
-#endif
     if constexpr (STK) wa[0][tl] = wf[(s * STK_TILES + tl) * 64];
   };
   using I0 = std::integral_constant<int, 0>;
@@ -717,9 +649,6 @@ __global__ __launch_bounds__(256 * KS, KS == 1 ? 2 : 1) void conv3d_split_fwd2_k
   auto epi0 = [&](int j, uint32_t row0, uint32_t yok) {
     const int mt = j / TYE, y = j % TYE;
     const int co = (chunk * MT + mt) * 16 + 4 * g;
-#if SYN_ABL & 32
-    yok = 0;
-#endif
     eoff[j % ENB] = (((yok >> y) & 1u) && co < Cout) ? row0 + (uint32_t)y * ystep + (uint32_t)(co * 4) : OOB;   // (row0, yok: of the half's rows)
     if constexpr (EPI >= 2)
       eb[j % ENB] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(radd, (int)eoff[j % ENB], 0, 0));
@@ -790,7 +719,6 @@ __global__ __launch_bounds__(256 * KS, KS == 1 ? 2 : 1) void conv3d_split_fwd2_k
       wload(wbase + (int64_t)half * WCHUNK, 0, 1);
       wload(wbase + (int64_t)half * WCHUNK, 0, 2);
     }
-    wfirst = false;
   }
   T2(1);
   for (int t = walk.pos; t < walk.end; t += walk.stride) {
@@ -811,9 +739,6 @@ __global__ __launch_bounds__(256 * KS, KS == 1 ? 2 : 1) void conv3d_split_fwd2_k
       const unsigned char* img = ldsh + buf * BUF2 + lbase;
       unsigned char* nimg = ldsh + (buf ^ 1) * BUF2;
       auto xload = [&](int s, int q) {
-#if SYN_ABL & 16
-        if (s != 0) return;
-#endif
 #pragma unroll
         for (int y = 0; y < TY; ++y) xb[q][y] = *reinterpret_cast<const u32x4*>(img + q * PLANE2 + koff[s] + y * (HX * 16));
       };
@@ -824,12 +749,8 @@ __global__ __launch_bounds__(256 * KS, KS == 1 ? 2 : 1) void conv3d_split_fwd2_k
           for (int y = 0; y < TY; ++y)
 #pragma unroll
             for (int mt = 0; mt < MT; ++mt)
-#if SYN_ABL & 64
-              acc[y][mt][0] += __uint_as_float(wa[qa][mt][0] ^ xb[qb][y][0]);
-#else
               acc[y][mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, wa[qa][mt]),
                                                                    __builtin_bit_cast(bf16x8, xb[qb][y]), acc[y][mt], 0, 0, 0);
-#endif
         }
       };
       auto mmt = [&](auto TL, auto QB) {  // STK: acc[.][tile TL] += (row tile TL) x (activation piece QB)
@@ -837,12 +758,8 @@ __global__ __launch_bounds__(256 * KS, KS == 1 ? 2 : 1) void conv3d_split_fwd2_k
         if constexpr (STK) {
 #pragma unroll
           for (int y = 0; y < TY; ++y)
-#if SYN_ABL & 64
-            acc[y][tl][0] += __uint_as_float(wa[0][tl][0] ^ xb[qb][y][0]);
-#else
             acc[y][tl] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, wa[0][tl]),
                                                                  __builtin_bit_cast(bf16x8, xb[qb][y]), acc[y][tl], 0, 0, 0);
-#endif
         }
       };
       xload(0, 2);
@@ -1092,31 +1009,17 @@ __global__ __launch_bounds__(512, 1) void conv3d_split_fwd3_kernel(const SplitFw
 #pragma unroll
     for (int i = 0; i < NL; ++i) {
       const uint32_t vo = (pmask[i] & bad) ? OOB : (uint32_t)(prel[i] + base);
-#if SYN_ABL & 1
-      hnx[i] = (f32x4){__uint_as_float(vo), 1.f, 2.f, 3.f};
-#else
       hnx[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rin, (int)vo, 0, 0));
-#endif
     }
   };
   typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
   uint32_t cp[6];
-#if SYN_ABL & 2
-  auto conv_a = [&](int i) { cp[0] = __float_as_uint(hst[i][0]); cp[1] = __float_as_uint(hst[i][1]); cp[2] = cp[0] ^ cp[1]; };
-  auto conv_b = [&](int i) { cp[3] = __float_as_uint(hst[i][2]); cp[4] = __float_as_uint(hst[i][3]); cp[5] = cp[3] ^ cp[4]; };
-#else
   auto conv_a = [&](int i) { syn_split3(hst[i][0], hst[i][1], cp[0], cp[1], cp[2]); };
   auto conv_b = [&](int i) { syn_split3(hst[i][2], hst[i][3], cp[3], cp[4], cp[5]); };
-#endif
   auto conv_c = [&](int i, unsigned char* dst) {
-#if SYN_ABL & 4
-    if (cp[0] == 0x12345u && cp[5] == 0x54321u)  // (never)
-#endif
-    {
     *reinterpret_cast<u32x2*>(dst + plds[i]) = (u32x2){cp[0], cp[3]};
     *reinterpret_cast<u32x2*>(dst + PLANE + plds[i]) = (u32x2){cp[1], cp[4]};
     *reinterpret_cast<u32x2*>(dst + 2 * PLANE + plds[i]) = (u32x2){cp[2], cp[5]};
-    }
   };
 
   // weight staging: piece j = tid + 512 k of the chunk's 3 x (7 MT KB) fragment blocks
@@ -1132,19 +1035,11 @@ __global__ __launch_bounds__(512, 1) void conv3d_split_fwd3_kernel(const SplitFw
     wsrc[k] = (q * piece_stride + chunk * ncc * NSTEP * MT * 64 + r) * 16;
   }
   u32x4 wst[C::NWL];
-  bool wfirst = true;
-  (void)wfirst;
   auto w_issue = [&](int cc) {
-#if SYN_ABL & 8
-    if (!wfirst) return;
-#endif
 #pragma unroll
     for (int k = 0; k < C::NWL; ++k) wst[k] = __builtin_amdgcn_raw_buffer_load_b128(rw, wsrc[k] + cc * (NSTEP * MT * 64 * 16), 0, 0);
   };
   auto w_store = [&](unsigned char* dst) {
-#if SYN_ABL & 8
-    if (!wfirst) return;
-#endif
 #pragma unroll
     for (int k = 0; k < C::NWL; ++k) {
       const int j = (tid + NTHR * k) >= C::NWP ? tid : tid + NTHR * k;
@@ -1175,9 +1070,6 @@ __global__ __launch_bounds__(512, 1) void conv3d_split_fwd3_kernel(const SplitFw
   auto item_off = [&](int j, uint32_t row0, uint32_t yok) -> uint32_t {
     const int mt = j / RW, y = j % RW;
     const int co = (chunk * MT + mt) * 16 + 4 * g;
-#if SYN_ABL & 32
-    yok = 0;
-#endif
     return (((yok >> y) & 1u) && co < Cout) ? row0 + (uint32_t)y * ystep + (uint32_t)(co * 4) : OOB;
   };
   auto addend_issue = [&](uint32_t row0, uint32_t yok) {
@@ -1245,7 +1137,6 @@ __global__ __launch_bounds__(512, 1) void conv3d_split_fwd3_kernel(const SplitFw
       conv_c(i, lds);
     }
     w_store(wlds);
-    wfirst = false;
     const int t1 = ncc > 1 ? walk.pos : walk.pos + walk.stride, c1 = ncc > 1 ? 1 : 0;
     halo_issue(t1, c1);
 #pragma unroll
@@ -1269,9 +1160,6 @@ __global__ __launch_bounds__(512, 1) void conv3d_split_fwd3_kernel(const SplitFw
     const unsigned char* wl = wlds + (WDB ? buf * C::WBYTES : 0) + lane * 16;
     auto frags = [&](auto SS, auto PP) {  // piece PP of the operands of step SS -> register set SS & 1
       constexpr int s = decltype(SS)::value, q = decltype(PP)::value;
-#if SYN_ABL & 16
-      if (s > 1) return;
-#endif
 #pragma unroll
       for (int mt = 0; mt < MT; ++mt)
         wa[s & 1][q][mt] = *reinterpret_cast<const u32x4*>(wl + ((q * NSTEP + s) * MT + mt) * 1024);
@@ -1284,12 +1172,8 @@ __global__ __launch_bounds__(512, 1) void conv3d_split_fwd3_kernel(const SplitFw
       for (int y = 0; y < RW; ++y)
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt)
-#if SYN_ABL & 64
-          acc[y][mt][0] += __uint_as_float(wa[s & 1][qa][mt][0] ^ xb[s & 1][qb][y][0]);
-#else
           acc[y][mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, wa[s & 1][qa][mt]),
                                                                __builtin_bit_cast(bf16x8, xb[s & 1][qb][y]), acc[y][mt], 0, 0, 0);
-#endif
     };
     using I0 = std::integral_constant<int, 0>;
     using I1 = std::integral_constant<int, 1>;
@@ -1582,24 +1466,69 @@ __global__ __launch_bounds__(512, 1) void conv3d_split_upfwd_kernel(const SplitF
   }
 }
 
-// grid widths (workgroups along x; y / z = channel chunks / parity groups).  Never narrower than the tile count where that is
-// possible: 296 workgroups for 300 tiles made 8 stragglers walk two tiles = twice the kernel's critical path.
-inline int split_upfwd_grid_x(int ntiles, int ngroups) {
-  int gx = std::max(8, ((256 / ngroups) / 8) * 8);  // one 512-thread workgroup per CU
-  while (gx > 8 && gx - 8 >= ntiles) gx -= 8;
-  if (ntiles < 8) gx = ntiles;
-  return gx;
-}
+// grid widths (workgroups along x; y / z = channel chunks / parity groups): common.h, syn_tile_grid_x
+inline int split_upfwd_grid_x(int ntiles, int ngroups) { return syn_tile_grid_x(256 / ngroups, ntiles); }  // one 512-thread workgroup per CU
+inline int split_grid_x(int ntiles, int nchunks) { return syn_tile_grid_x(512 / nchunks, ntiles); }        // 2 workgroups per CU in total
 inline int split_wgrad_grid_x(int ntiles, int gy) {
   int gx = std::max(1, 256 / gy);  // one 512-thread workgroup per CU
   if (gx > ntiles) gx = ntiles;
   return gx;
 }
-inline int split_grid_x(int ntiles, int nchunks) {
-  int gx = std::max(8, ((512 / nchunks) / 8) * 8);  // 2 workgroups per CU in total
-  while (gx > 8 && gx - 8 >= ntiles) gx -= 8;
-  if (ntiles < 8) gx = ntiles;
-  return gx;
+
+inline int split_tiles1(const int s[3]) { return (s[1] + TY - 1) / TY; }
+inline int split_tiles2(const int s[3]) { return (s[2] + TX - 1) / TX; }
+inline int split_ntiles(const int s[3]) { return ((s[0] + TZ - 1) / TZ) * split_tiles1(s) * split_tiles2(s); }
+
+inline SplitFwdArgs split_fwd_args(const float* in, const float* wp, const float* bias, const float* addend, float* out,
+                                   float* stats_partial, const int s[3], int Cin, int Cout, int act, int stacked) {
+  SplitFwdArgs a;
+  a.in = in;
+  a.wp = reinterpret_cast<const u32x4*>(wp);
+  a.bias = bias;
+  a.addend = addend;
+  a.out = out;
+  a.stats_partial = stats_partial;
+  a.D0 = s[0]; a.D1 = s[1]; a.D2 = s[2];
+  a.Cin = Cin; a.Cout = Cout; a.ncc = Cin / 8;
+  a.tiles1 = split_tiles1(s);
+  a.tiles2 = split_tiles2(s);
+  a.ntiles = split_ntiles(s);
+  a.act = act;
+  a.stacked = stacked;
+  return a;
+}
+
+// run-time values -> compile-time constants: f(std::integral_constant<int, MT>) for mt = 1, 2, 3 ...
+template <class F>
+int with_mt(int mt, F&& f) {
+  if (mt == 1) return f(std::integral_constant<int, 1>{});
+  if (mt == 2) return f(std::integral_constant<int, 2>{});
+  return f(std::integral_constant<int, 3>{});
+}
+// ... and f(std::integral_constant<int, EPI>) for the epilogue of the fwd2 / fwd3 kernels: act 0-4 with or without an addend.  A
+// launch with statistics (ST) has no addend and no derivative epilogue: EPI 0, 1 and 5 are all it instantiates.
+inline int split_epi(const SplitFwdArgs& a) {
+  if (a.act == 3) return a.addend ? 7 : 5;
+  if (a.act == 4) return 6;
+  return a.act + ((a.addend && a.act < 2) ? 3 : 0);
+}
+template <bool ST, class F>
+int with_epi(int epi, F&& f) {
+  if constexpr (ST) {
+    if (epi == 5) return f(std::integral_constant<int, 5>{});
+    return epi == 1 ? f(std::integral_constant<int, 1>{}) : f(std::integral_constant<int, 0>{});
+  } else {
+    switch (epi) {
+      case 0: return f(std::integral_constant<int, 0>{});
+      case 1: return f(std::integral_constant<int, 1>{});
+      case 2: return f(std::integral_constant<int, 2>{});
+      case 3: return f(std::integral_constant<int, 3>{});
+      case 5: return f(std::integral_constant<int, 5>{});
+      case 6: return f(std::integral_constant<int, 6>{});
+      case 7: return f(std::integral_constant<int, 7>{});
+      default: return f(std::integral_constant<int, 4>{});
+    }
+  }
 }
 
 // act 3 / 4 (ReLU family): the RELU instantiation of the generic kernels under the ELU family's codes 1 / 2
@@ -1610,158 +1539,89 @@ inline bool relu_args(const SplitFwdArgs& a, SplitFwdArgs& b) {
   return true;
 }
 
-template <int MT, int NPAR, int NPROD>
-int launch_split_upfwd_np(const SplitFwdArgs& a0, hipStream_t st) {
-  constexpr int NG = 8 / NPAR;
-  SplitFwdArgs a;
-  const bool relu = relu_args(a0, a);
-  const int gx = split_upfwd_grid_x(a.ntiles, NG);
-  const size_t smem = 2 * BUF;
-  auto kern = relu ? conv3d_split_upfwd_kernel<MT, NPAR, NPROD, true> : conv3d_split_upfwd_kernel<MT, NPAR, NPROD>;
-  static SynOncePerDevice attr_done, attr_done_r;
-  if (auto once_ = (relu ? attr_done_r : attr_done).first()) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-  }
-  hipLaunchKernelGGL(kern, dim3(gx, 1, NG), dim3(512), smem, st, a);
-  return hipGetLastError() == hipSuccess ? SYNTHSR_OK : SYNTHSR_ELAUNCH;
-}
-
 template <int MT, int NPAR>
-int launch_split_upfwd(const SplitFwdArgs& a, hipStream_t st) {
-  return t_nprod == 9 ? launch_split_upfwd_np<MT, NPAR, 9>(a, st) : launch_split_upfwd_np<MT, NPAR, 6>(a, st);
-}
-
-template <int MT, bool ST, int UPM, int NPROD>
-int launch_split_fwd_np(const SplitFwdArgs& a0, int gx, int nchunks, hipStream_t st) {
+int launch_split_upfwd(const SplitFwdArgs& a0, int nprod, hipStream_t st) {
+  constexpr int NG = 8 / NPAR;
+  constexpr auto k9r = conv3d_split_upfwd_kernel<MT, NPAR, 9, true>, k9 = conv3d_split_upfwd_kernel<MT, NPAR, 9>;
+  constexpr auto k6r = conv3d_split_upfwd_kernel<MT, NPAR, 6, true>, k6 = conv3d_split_upfwd_kernel<MT, NPAR, 6>;
   SplitFwdArgs a;
   const bool relu = relu_args(a0, a);
-  const size_t smem = 2 * BUF;
-  auto kern = relu ? conv3d_split_fwd_kernel<MT, ST, UPM, NPROD, true> : conv3d_split_fwd_kernel<MT, ST, UPM, NPROD>;
-  static SynOncePerDevice attr_done, attr_done_r;
-  if (auto once_ = (relu ? attr_done_r : attr_done).first()) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-  }
-  hipLaunchKernelGGL(kern, dim3(gx, nchunks), dim3(256), smem, st, a);
-  return hipGetLastError() == hipSuccess ? SYNTHSR_OK : SYNTHSR_ELAUNCH;
+  const dim3 grid(split_upfwd_grid_x(a.ntiles, NG), 1, NG);
+  if (nprod == 9) launch_smem<k9, k9r>(relu, grid, dim3(512), 2 * BUF, st, a);
+  else launch_smem<k6, k6r>(relu, grid, dim3(512), 2 * BUF, st, a);
+  SYN_CHECK_LAUNCH();
+  return SYNTHSR_OK;
 }
 
-// split-K halves (conv3d_split_fwd2_kernel<..., KS = 2>): the launch leaves CUs single-occupied anyway (at most one 4-wave
-// workgroup per CU) and the chunk count is even
-inline bool split_fwd2_uses_halves(int gx, int nchunks, int ncc) {
-  return (int64_t)gx * nchunks <= 256 && ncc >= 4 && (ncc % 2) == 0;
-}
-
-template <int MT, bool ST, int EPI, bool STK>
-int launch_split_fwd2_e(const SplitFwdArgs& a, int gx, int nchunks, hipStream_t st) {
-  if constexpr (!STK) {
-    if (split_fwd2_uses_halves(gx, nchunks, a.ncc)) {
-      const size_t smem2 = 4 * BUF2 + MT * 16 * 4;
-      auto kern2 = conv3d_split_fwd2_kernel<MT, ST, EPI, false, 2>;
-      static SynOncePerDevice attr2_done;
-      if (auto once_ = attr2_done.first()) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern2), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem2);
-      }
-      hipLaunchKernelGGL(kern2, dim3(gx, nchunks), dim3(512), smem2, st, a);
-      return hipGetLastError() == hipSuccess ? SYNTHSR_OK : SYNTHSR_ELAUNCH;
-    }
-  }
-  const size_t smem = 2 * BUF2 + MT * 16 * 4;
-  auto kern = conv3d_split_fwd2_kernel<MT, ST, EPI, STK>;
-  static SynOncePerDevice attr_done;
-  if (auto once_ = attr_done.first()) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-  }
-  hipLaunchKernelGGL(kern, dim3(gx, nchunks), dim3(256), smem, st, a);
-  return hipGetLastError() == hipSuccess ? SYNTHSR_OK : SYNTHSR_ELAUNCH;
-}
-
-// EPI of the fwd2 / fwd3 kernels for act 0-4 with or without an addend
-inline int split_epi(const SplitFwdArgs& a) {
-  if (a.act == 3) return a.addend ? 7 : 5;
-  if (a.act == 4) return 6;
-  return a.act + ((a.addend && a.act < 2) ? 3 : 0);
-}
-
-template <int MT, bool ST, bool STK = false>
-int launch_split_fwd2(const SplitFwdArgs& a, int gx, int nchunks, hipStream_t st) {
-  const int epi = split_epi(a);
-  if constexpr (ST) {
-    if (epi == 5) return launch_split_fwd2_e<MT, true, 5, STK>(a, gx, nchunks, st);
-    return epi == 1 ? launch_split_fwd2_e<MT, true, 1, STK>(a, gx, nchunks, st) : launch_split_fwd2_e<MT, true, 0, STK>(a, gx, nchunks, st);
-  } else {
-    switch (epi) {
-      case 0: return launch_split_fwd2_e<MT, false, 0, STK>(a, gx, nchunks, st);
-      case 1: return launch_split_fwd2_e<MT, false, 1, STK>(a, gx, nchunks, st);
-      case 2: return launch_split_fwd2_e<MT, false, 2, STK>(a, gx, nchunks, st);
-      case 3: return launch_split_fwd2_e<MT, false, 3, STK>(a, gx, nchunks, st);
-      case 5: return launch_split_fwd2_e<MT, false, 5, STK>(a, gx, nchunks, st);
-      case 6: return launch_split_fwd2_e<MT, false, 6, STK>(a, gx, nchunks, st);
-      case 7: return launch_split_fwd2_e<MT, false, 7, STK>(a, gx, nchunks, st);
-      default: return launch_split_fwd2_e<MT, false, 4, STK>(a, gx, nchunks, st);
-    }
-  }
-}
-
-// which forward kernel (measured, profiles/r04_split_fwd_variants.txt): the 4-wave kernel with two workgroups per CU, except
-// where the layer has between one and two rounds of its 512 workgroup slots AND several co-chunks (40^3, 96 output channels:
-// 600 units): there the 8-wave kernel (one workgroup per CU, weights through LDS) quantises better (-10 %); with fewer units
-// than slots (20^3, 192 output channels: 200) the 4-wave kernel wins again (0.126 vs 0.14 ms)
-// Round 6: a layer that syn_split_plan_mt re-planned onto 32-channel co-chunks (40^3, 96 output channels: 900 units) stays on the
-// 4-wave kernel -- 0.200 / 0.193 ms against 0.234 / 0.218 for the 8-wave kernel on 600 units, same box
-// (profiles/r06_plan_40cubed_ab.txt)
-inline bool split_uses_fwd3(int ntiles, int nchunks, int mt = 3, int Cout = 0) {
+// Which forward / data-gradient kernel a call takes.  ONE statement of it: launch_split_fwd launches by it, the statistics pass of
+// syn_split_fwd takes its number of workgroup columns from it, synthsr_conv3d_plan reports it (syn_split_fwd_halves).
+//  * generic: conv3d_split_fwd_kernel -- nine products, and the data gradient of a folded decoder conv (upm = 2);
+//  * fwd2: conversion inside the K loop, the 4-wave kernel with two workgroups per CU; the stacked 24-channel layout is its alone
+//    (the layout decides the kernel: conv3d.hip plans it only for 6 products, Cout = 24, one co-chunk of mt = 2);
+//  * fwd2_halves: its split-K form (KS = 2) where the launch leaves CUs single-occupied anyway (at most one 4-wave workgroup per
+//    CU) and the chunk count is even;
+//  * fwd3 (measured, profiles/r04_split_fwd_variants.txt): where the layer has between one and two rounds of its 512 workgroup slots
+//    AND several co-chunks (40^3, 96 output channels: 600 units) the 8-wave kernel (one workgroup per CU, weights through LDS)
+//    quantises better (-10 %); with fewer units than slots (20^3, 192 output channels: 200) the 4-wave kernel wins again (0.126 vs
+//    0.14 ms).  Round 6: a layer that syn_split_plan_mt re-planned onto 32-channel co-chunks (40^3, 96 output channels: 900 units)
+//    stays on the 4-wave kernel -- 0.200 / 0.193 ms against 0.234 / 0.218 for the 8-wave kernel on 600 units, same box
+//    (profiles/r06_plan_40cubed_ab.txt).
+enum class FwdRoute { generic, fwd2, fwd2_halves, fwd3, refuse };
+inline FwdRoute split_fwd_route(int ntiles, int nchunks, int ncc, int mt, int Cout, int stacked, int upm, int nprod) {
+  if (stacked) return (upm == 0 && mt == 2 && nprod == 6) ? FwdRoute::fwd2 : FwdRoute::refuse;
+  if (upm != 0 || nprod != 6) return FwdRoute::generic;
   const int64_t units = (int64_t)ntiles * nchunks;
-  if (syn_split_replanned(ntiles, (Cout + 15) / 16, mt)) return false;
-  return nchunks >= 2 && units >= 512 && units < 1024;
+  if (!syn_split_replanned(ntiles, (Cout + 15) / 16, mt) && nchunks >= 2 && units >= 512 && units < 1024) return FwdRoute::fwd3;
+  const bool halves = (int64_t)split_grid_x(ntiles, nchunks) * nchunks <= 256 && ncc >= 4 && (ncc % 2) == 0;
+  return halves ? FwdRoute::fwd2_halves : FwdRoute::fwd2;
+}
+// workgroups along x of the route's launch (= the workgroup columns that write statistics partials)
+inline int split_fwd_grid_x(FwdRoute route, int ntiles, int nchunks) {
+  return route == FwdRoute::fwd3 ? split_upfwd_grid_x(ntiles, nchunks) : split_grid_x(ntiles, nchunks);
 }
 
-template <int MT, bool ST, int EPI>
-int launch_split_fwd3_e(const SplitFwdArgs& a, int nchunks, hipStream_t st) {
-  const int gx = split_upfwd_grid_x(a.ntiles, nchunks);  // one 512-thread workgroup per CU
-  const size_t smem = F3Cfg<MT>::SMEM;
-  auto kern = conv3d_split_fwd3_kernel<MT, ST, EPI>;
-  static SynOncePerDevice attr_done;
-  if (auto once_ = attr_done.first()) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-  }
-  hipLaunchKernelGGL(kern, dim3(gx, nchunks), dim3(512), smem, st, a);
-  return hipGetLastError() == hipSuccess ? SYNTHSR_OK : SYNTHSR_ELAUNCH;
+template <auto Kern>
+int launch_split_fwd_k(const SplitFwdArgs& a, dim3 grid, int threads, size_t smem, hipStream_t st) {
+  max_dyn_smem<Kern>(smem);
+  hipLaunchKernelGGL(Kern, grid, dim3(threads), smem, st, a);
+  SYN_CHECK_LAUNCH();
+  return SYNTHSR_OK;
 }
 
-template <int MT, bool ST>
-int launch_split_fwd3(const SplitFwdArgs& a, int nchunks, hipStream_t st) {
-  const int epi = split_epi(a);
-  if constexpr (ST) {
-    if (epi == 5) return launch_split_fwd3_e<MT, true, 5>(a, nchunks, st);
-    return epi == 1 ? launch_split_fwd3_e<MT, true, 1>(a, nchunks, st) : launch_split_fwd3_e<MT, true, 0>(a, nchunks, st);
-  } else {
-    switch (epi) {
-      case 0: return launch_split_fwd3_e<MT, false, 0>(a, nchunks, st);
-      case 1: return launch_split_fwd3_e<MT, false, 1>(a, nchunks, st);
-      case 2: return launch_split_fwd3_e<MT, false, 2>(a, nchunks, st);
-      case 3: return launch_split_fwd3_e<MT, false, 3>(a, nchunks, st);
-      case 5: return launch_split_fwd3_e<MT, false, 5>(a, nchunks, st);
-      case 6: return launch_split_fwd3_e<MT, false, 6>(a, nchunks, st);
-      case 7: return launch_split_fwd3_e<MT, false, 7>(a, nchunks, st);
-      default: return launch_split_fwd3_e<MT, false, 4>(a, nchunks, st);
-    }
-  }
-}
-
-template <int MT, bool ST, int UPM = 0>
-int launch_split_fwd(const SplitFwdArgs& a, int gx, int nchunks, hipStream_t st) {
-  if (a.stacked) {  // the layout decides the kernel (conv3d.hip plans it only for 6 products, Cout = 24, one co-chunk)
-    if constexpr (UPM == 0 && MT == 2) return launch_split_fwd2<2, ST, true>(a, gx, nchunks, st);
-    return SYNTHSR_EINVAL;
-  }
+template <int MT, bool ST, int UPM>
+int launch_split_fwd(const SplitFwdArgs& a0, FwdRoute route, int nchunks, int nprod, hipStream_t st) {
+  if (route == FwdRoute::refuse) return SYNTHSR_EINVAL;
+  const dim3 grid(split_fwd_grid_x(route, a0.ntiles, nchunks), nchunks);
   if constexpr (UPM == 0) {
-    if (t_nprod == 6 && split_uses_fwd3(a.ntiles, nchunks, MT, a.Cout)) return launch_split_fwd3<MT, ST>(a, nchunks, st);
-    if (t_nprod == 6) return launch_split_fwd2<MT, ST>(a, gx, nchunks, st);
+    const int epi = split_epi(a0);
+    if (a0.stacked) {
+      if constexpr (MT == 2)
+        return with_epi<ST>(epi, [&](auto E) {
+          return launch_split_fwd_k<conv3d_split_fwd2_kernel<2, ST, decltype(E)::value, true>>(a0, grid, 256, 2 * BUF2 + 2 * 16 * 4, st);
+        });
+      return SYNTHSR_EINVAL;
+    }
+    if (route == FwdRoute::fwd3)
+      return with_epi<ST>(epi, [&](auto E) {
+        return launch_split_fwd_k<conv3d_split_fwd3_kernel<MT, ST, decltype(E)::value>>(a0, grid, 512, F3Cfg<MT>::SMEM, st);
+      });
+    if (route != FwdRoute::generic)
+      return with_epi<ST>(epi, [&](auto E) {
+        constexpr int EPI = decltype(E)::value;
+        if (route == FwdRoute::fwd2_halves)
+          return launch_split_fwd_k<conv3d_split_fwd2_kernel<MT, ST, EPI, false, 2>>(a0, grid, 512, 4 * BUF2 + MT * 16 * 4, st);
+        return launch_split_fwd_k<conv3d_split_fwd2_kernel<MT, ST, EPI, false>>(a0, grid, 256, 2 * BUF2 + MT * 16 * 4, st);
+      });
   }
-  return t_nprod == 9 ? launch_split_fwd_np<MT, ST, UPM, 9>(a, gx, nchunks, st) : launch_split_fwd_np<MT, ST, UPM, 6>(a, gx, nchunks, st);
+  constexpr auto k9r = conv3d_split_fwd_kernel<MT, ST, UPM, 9, true>, k9 = conv3d_split_fwd_kernel<MT, ST, UPM, 9>;
+  constexpr auto k6r = conv3d_split_fwd_kernel<MT, ST, UPM, 6, true>, k6 = conv3d_split_fwd_kernel<MT, ST, UPM, 6>;
+  SplitFwdArgs a;
+  const bool relu = relu_args(a0, a);
+  if (nprod == 9) launch_smem<k9, k9r>(relu, grid, dim3(256), 2 * BUF, st, a);
+  else launch_smem<k6, k6r>(relu, grid, dim3(256), 2 * BUF, st, a);
+  SYN_CHECK_LAUNCH();
+  return SYNTHSR_OK;
 }
-
-
 
 // ------------------------------------------------------------------------------------------------ weight gradient
 //   dW[tap][ci][co] = sum over voxels v of x[v + tap - 1][ci] * dz[v][co]:  D[(tap, ci)][co] += sum over the 6 (i, j) of
@@ -2194,29 +2054,26 @@ int launch_split_wgrad_np(const SplitWgArgs& a0, hipStream_t st) {
   const int gy = a.ncc * a.nco;
   const int gx = split_wgrad_grid_x(a.ntiles, gy);
   const size_t smem = (size_t)C::NBUF * C::BUFB;
-  auto kern = conv3d_split_wgrad_kernel<COW, NPROD, STK, CIW>;
-  static SynOncePerDevice attr_done;
-  if (auto once_ = attr_done.first()) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-  }
+  constexpr auto kern = conv3d_split_wgrad_kernel<COW, NPROD, STK, CIW>;
+  max_dyn_smem<kern>(smem);
   DetRun det;
   if (const int rc_ = syn_det_prepare(&det, &a.dw, &a.dbias, (int64_t)27 * a.cin_total * a.Cout, a.Cout, gx, st)) return rc_;
   a.det_stride = det.stride;
   hipLaunchKernelGGL(kern, dim3(gx, gy), dim3(512), smem, st, a);
-  if (hipGetLastError() != hipSuccess) return SYNTHSR_ELAUNCH;
+  SYN_CHECK_LAUNCH();
   return syn_det_finish(&det, st);
 }
 
 template <int COW>
-int launch_split_wgrad(const SplitWgArgs& a, hipStream_t st) {
+int launch_split_wgrad(const SplitWgArgs& a, int nprod, hipStream_t st) {
   if constexpr (COW == 24) {
-    if (t_nprod == 6 && a.ciw == 24) return launch_split_wgrad_np<24, 6, true, 24>(a, st);
-    if (t_nprod == 6) return launch_split_wgrad_np<24, 6, true>(a, st);
+    if (nprod == 6 && a.ciw == 24) return launch_split_wgrad_np<24, 6, true, 24>(a, st);
+    if (nprod == 6) return launch_split_wgrad_np<24, 6, true>(a, st);
   }
   if constexpr (COW == 48) {
-    if (t_nprod == 6 && a.ciw == 16) return launch_split_wgrad_np<48, 6, false, 16>(a, st);
+    if (nprod == 6 && a.ciw == 16) return launch_split_wgrad_np<48, 6, false, 16>(a, st);
   }
-  return t_nprod == 9 ? launch_split_wgrad_np<COW, 9>(a, st) : launch_split_wgrad_np<COW, 6>(a, st);
+  return nprod == 9 ? launch_split_wgrad_np<COW, 9>(a, st) : launch_split_wgrad_np<COW, 6>(a, st);
 }
 
 // ---- weight gradient of the up-sampled channel range of a FOLDED decoder conv (round 6; unet.py; ext/neuron/models.py:426-444
@@ -2485,22 +2342,18 @@ extern "C" __attribute__((visibility("hidden"))) int syn_split_upwgrad(const flo
   a.Cin = Cin; a.Cout = Cout;
   a.ncc = Cin / 16;
   a.nco = Cout / 24;
-  a.tiles1 = (s[1] + TY - 1) / TY;
-  a.tiles2 = (s[2] + TX - 1) / TX;
-  a.ntiles = ((s[0] + TZ - 1) / TZ) * a.tiles1 * a.tiles2;
+  a.tiles1 = split_tiles1(s);
+  a.tiles2 = split_tiles2(s);
+  a.ntiles = split_ntiles(s);
   const int gy = a.ncc * a.nco;
   const int gx = split_wgrad_grid_x(a.ntiles, gy);
-  static SynOncePerDevice attr_done;
-  if (auto once_ = attr_done.first()) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv3d_split_upwgrad_kernel),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)UW_LDS);
-  }
+  max_dyn_smem<conv3d_split_upwgrad_kernel>(UW_LDS);
   DetRun det;
   float* no_dbias = nullptr;
   if (const int rc_ = syn_det_prepare(&det, &a.dwc, &no_dbias, (int64_t)8 * 27 * Cin * Cout, Cout, gx, st)) return rc_;
   a.det_stride = det.stride;
   hipLaunchKernelGGL(conv3d_split_upwgrad_kernel, dim3(gx, gy), dim3(512), (size_t)UW_LDS, st, a);
-  if (hipGetLastError() != hipSuccess) return SYNTHSR_ELAUNCH;
+  SYN_CHECK_LAUNCH();
   return syn_det_finish(&det, st);
 }
 
@@ -2521,60 +2374,38 @@ extern "C" int synthsr_split_tile_schedule(int kernel, int ntiles, int ny, int b
   return SYNTHSR_OK;
 }
 
+// does the forward / data-gradient launch of this plain layer run as split-K halves (reported by synthsr_conv3d_plan)?  The plan
+// asks before it has settled mt and Cout, as for three tiles per co-chunk of a layer that syn_split_plan_mt did not re-plan.
+extern "C" __attribute__((visibility("hidden"))) int syn_split_fwd_halves(const int s[3], int Cin, int nchunks, int stacked,
+                                                                           int nprod) {
+  return split_fwd_route(split_ntiles(s), nchunks, Cin / 8, 3, 0, stacked, 0, nprod) == FwdRoute::fwd2_halves ? 1 : 0;
+}
+
 // called by conv3d.hip's dispatcher when the plan of the layer says `split` (weights packed in the split layout by pack_value).
 // stats != null: BatchNorm batch statistics (mean | biased variance) of the output, from per-workgroup sums in `partial`
 // (room for 512 x 2 Cout floats)
 // upm = 2: the data gradient of a folded decoder conv (`in` = dz on the 2x grid, s = the low-resolution grid, wp = 8 parity sets)
-// does the six-product forward / data-gradient launch of this plain layer run as split-K halves (reported by synthsr_conv3d_plan)?
-extern "C" __attribute__((visibility("hidden"))) int syn_split_fwd_halves(const int s[3], int Cin, int nchunks, int stacked,
-                                                                           int nprod) {
-  const int ntiles = ((s[0] + TZ - 1) / TZ) * ((s[1] + TY - 1) / TY) * ((s[2] + TX - 1) / TX);
-  if (stacked || nprod != 6 || split_uses_fwd3(ntiles, nchunks, 3, 0)) return 0;
-  return split_fwd2_uses_halves(split_grid_x(ntiles, nchunks), nchunks, Cin / 8) ? 1 : 0;
-}
-
 extern "C" __attribute__((visibility("hidden"))) int syn_split_fwd(const float* in, const float* wp, const float* bias,
                                                                     const float* addend, float* out, const int s[3], int Cin,
                                                                     int Cout, int mt, int nchunks, int act, float* stats,
                                                                     float* partial, int upm, int stacked, int nprod,
                                                                     hipStream_t st) {
   if (nprod != 6 && nprod != 9) return SYNTHSR_EINVAL;
-  t_nprod = nprod;
   if ((Cin % 8) != 0 || (Cout % 4) != 0 || mt < 1 || mt > 3 || nchunks < 1 || (upm != 0 && upm != 2)) return SYNTHSR_EINVAL;
-  if (stacked && (Cout != 24 || mt != 2 || nchunks != 1 || upm != 0 || t_nprod != 6)) return SYNTHSR_EINVAL;
+  if (stacked && (Cout != 24 || mt != 2 || nchunks != 1 || upm != 0 || nprod != 6)) return SYNTHSR_EINVAL;
   if (act < 0 || act > 4 || (stats && (!partial || addend || act == 2 || act == 4 || upm))) return SYNTHSR_EINVAL;
   if (upm && (bias || addend || act != 0)) return SYNTHSR_EINVAL;
   const int64_t vox = (int64_t)s[0] * s[1] * s[2];
   if ((upm ? 8 : 1) * vox * Cin * 4 >= (1ll << 31) || vox * Cout * 4 >= (1ll << 31)) return SYNTHSR_EINVAL;
-  SplitFwdArgs a;
-  a.in = in;
-  a.wp = reinterpret_cast<const u32x4*>(wp);
-  a.bias = bias;
-  a.addend = addend;
-  a.out = out;
-  a.stats_partial = stats ? partial : nullptr;
-  a.D0 = s[0]; a.D1 = s[1]; a.D2 = s[2];
-  a.Cin = Cin; a.Cout = Cout; a.ncc = Cin / 8;
-  a.tiles1 = (s[1] + TY - 1) / TY;
-  a.tiles2 = (s[2] + TX - 1) / TX;
-  a.ntiles = ((s[0] + TZ - 1) / TZ) * a.tiles1 * a.tiles2;
-  a.act = act;
-  a.stacked = stacked;
-  const int gx = split_grid_x(a.ntiles, nchunks);
-  int rc;
+  const SplitFwdArgs a = split_fwd_args(in, wp, bias, addend, out, stats ? partial : nullptr, s, Cin, Cout, act, stacked);
+  const FwdRoute route = split_fwd_route(a.ntiles, nchunks, a.ncc, mt, Cout, stacked, upm, nprod);
   if (stats) {
-    rc = mt == 1 ? launch_split_fwd<1, true>(a, gx, nchunks, st)
-                 : (mt == 2 ? launch_split_fwd<2, true>(a, gx, nchunks, st) : launch_split_fwd<3, true>(a, gx, nchunks, st));
+    const int rc = with_mt(mt, [&](auto M) { return launch_split_fwd<decltype(M)::value, true, 0>(a, route, nchunks, nprod, st); });
     if (rc != SYNTHSR_OK) return rc;
-    const int gcols = (!stacked && t_nprod == 6 && split_uses_fwd3(a.ntiles, nchunks, mt, Cout)) ? split_upfwd_grid_x(a.ntiles, nchunks) : gx;  // workgroup columns that wrote partials
-    return synthsr_bn_stats_from_partials(partial, gcols, vox, Cout, stats, (synthsr_stream_t)st);
+    return synthsr_bn_stats_from_partials(partial, split_fwd_grid_x(route, a.ntiles, nchunks), vox, Cout, stats, (synthsr_stream_t)st);
   }
-  if (upm == 2)
-    return mt == 1 ? launch_split_fwd<1, false, 2>(a, gx, nchunks, st)
-                   : (mt == 2 ? launch_split_fwd<2, false, 2>(a, gx, nchunks, st) : launch_split_fwd<3, false, 2>(a, gx, nchunks, st));
-  rc = mt == 1 ? launch_split_fwd<1, false>(a, gx, nchunks, st)
-               : (mt == 2 ? launch_split_fwd<2, false>(a, gx, nchunks, st) : launch_split_fwd<3, false>(a, gx, nchunks, st));
-  return rc;
+  if (upm == 2) return with_mt(mt, [&](auto M) { return launch_split_fwd<decltype(M)::value, false, 2>(a, route, nchunks, nprod, st); });
+  return with_mt(mt, [&](auto M) { return launch_split_fwd<decltype(M)::value, false, 0>(a, route, nchunks, nprod, st); });
 }
 
 // forward pass of the up-sampled channel range of a folded decoder conv: lo [s][Cin] -> out [2 s][Cout] (Cout <= 48: one co-chunk),
@@ -2583,27 +2414,13 @@ extern "C" __attribute__((visibility("hidden"))) int syn_split_upfwd(const float
                                                                       const float* addend, float* out, const int s[3], int Cin,
                                                                       int Cout, int mt, int act, int nprod, hipStream_t st) {
   if (nprod != 6 && nprod != 9) return SYNTHSR_EINVAL;
-  t_nprod = nprod;
   if ((Cin % 8) != 0 || (Cout % 4) != 0 || mt < 1 || mt > 3 || Cout > 16 * mt || (act != 0 && act != 1 && act != 3)) return SYNTHSR_EINVAL;
   const int64_t vox = (int64_t)s[0] * s[1] * s[2];
   if (vox * Cin * 4 >= (1ll << 31) || 8 * vox * Cout * 4 >= (1ll << 31)) return SYNTHSR_EINVAL;
-  SplitFwdArgs a;
-  a.in = lo;
-  a.wp = reinterpret_cast<const u32x4*>(wp);
-  a.bias = bias;
-  a.addend = addend;
-  a.out = out;
-  a.stats_partial = nullptr;
-  a.D0 = s[0]; a.D1 = s[1]; a.D2 = s[2];
-  a.Cin = Cin; a.Cout = Cout; a.ncc = Cin / 8;
-  a.tiles1 = (s[1] + TY - 1) / TY;
-  a.tiles2 = (s[2] + TX - 1) / TX;
-  a.ntiles = ((s[0] + TZ - 1) / TZ) * a.tiles1 * a.tiles2;
-  a.act = act;
-  a.stacked = 0;
-  if (mt == 1) return launch_split_upfwd<1, 4>(a, st);
-  if (mt == 2) return launch_split_upfwd<2, 4>(a, st);
-  return launch_split_upfwd<3, 2>(a, st);
+  const SplitFwdArgs a = split_fwd_args(lo, wp, bias, addend, out, nullptr, s, Cin, Cout, act, 0);
+  if (mt == 1) return launch_split_upfwd<1, 4>(a, nprod, st);
+  if (mt == 2) return launch_split_upfwd<2, 4>(a, nprod, st);
+  return launch_split_upfwd<3, 2>(a, nprod, st);
 }
 
 // weight gradient of the input-channel range [ci_off, ci_off + Cin) of a layer with cin_total input channels (+ optionally the
@@ -2612,7 +2429,6 @@ extern "C" __attribute__((visibility("hidden"))) int syn_split_wgrad(const float
                                                                       const int s[3], int cin_total, int ci_off, int Cin,
                                                                       int Cout, int nprod, hipStream_t st) {
   if (nprod != 6 && nprod != 9) return SYNTHSR_EINVAL;
-  t_nprod = nprod;
   if ((Cin % 8) != 0 || (Cout % 24) != 0) return SYNTHSR_EINVAL;
   const int64_t vox = (int64_t)s[0] * s[1] * s[2];
   if (vox * Cin * 4 >= (1ll << 31) || vox * Cout * 4 >= (1ll << 31)) return SYNTHSR_EINVAL;
@@ -2623,17 +2439,17 @@ extern "C" __attribute__((visibility("hidden"))) int syn_split_wgrad(const float
   a.dbias = dbias;
   a.D0 = s[0]; a.D1 = s[1]; a.D2 = s[2];
   a.Cin = Cin; a.Cout = Cout; a.cin_total = cin_total; a.ci_off = ci_off;
-  // 48-wide workgroups where they divide Cout (measured in round 3: 10 % faster than 2 x 24 padded column chunks)
+  // 48-wide workgroups where they divide Cout (measured in round 3: 10 % faster than 2 x 24 padded column chunks) ...
   const bool c48 = (Cout % 48) == 0;
-  // ... with 16 input channels each where those divide Cin (six products; option 12 bit 2 switches it off for A/B runs)
-  a.ciw = (c48 && (Cin % 16) == 0 && t_nprod == 6) ? 16 : 8;
-  // the stacked 24-column kernel with all 24 input channels in one workgroup (option 12 bit 3 switches it off for A/B runs)
-  if (!c48 && Cin == 24 && t_nprod == 6) a.ciw = 24;
+  // ... with 16 input channels each where those divide Cin (six products: profiles/r04_split_wgrad_ciw16_ab.txt)
+  a.ciw = (c48 && (Cin % 16) == 0 && nprod == 6) ? 16 : 8;
+  // 24 columns, Cin = 24, six products: the stacked kernel with all input channels in one workgroup (r04_split_wgrad_ciw24_ab.txt)
+  if (!c48 && Cin == 24 && nprod == 6) a.ciw = 24;
   a.ncc = Cin / a.ciw;
   a.nco = c48 ? Cout / 48 : Cout / 24;
-  a.tiles1 = (s[1] + TY - 1) / TY;
-  a.tiles2 = (s[2] + TX - 1) / TX;
-  a.ntiles = ((s[0] + TZ - 1) / TZ) * a.tiles1 * a.tiles2;
+  a.tiles1 = split_tiles1(s);
+  a.tiles2 = split_tiles2(s);
+  a.ntiles = split_ntiles(s);
   a.det_stride = 0;
-  return c48 ? launch_split_wgrad<48>(a, st) : launch_split_wgrad<24>(a, st);
+  return c48 ? launch_split_wgrad<48>(a, nprod, st) : launch_split_wgrad<24>(a, nprod, st);
 }

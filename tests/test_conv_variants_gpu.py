@@ -1,7 +1,7 @@
 """Every forward and data-gradient conv variant on its own against float64.
 
 One table (CASES) reaches every kernel the forward dispatchers know (csrc/conv3d.hip plan_fwd / dispatch_fwd2 / launch_fwd /
-parity_split, csrc/conv_split.hip launch_split_fwd / split_uses_fwd3 / split_fwd2_uses_halves, csrc/common.h syn_split_plan_mt,
+parity_split, csrc/conv_split.hip split_fwd_route / launch_split_fwd, csrc/common.h syn_split_plan_mt,
 csrc/conv_bf16.hip plan_bf16 and the split-K rule of synthsr_conv3d_bf16_fwd_ex) at the smallest shape its rule admits, ragged in
 every axis the rule allows.  Every row states its route; _route restates the dispatcher's rules, the tests assert
 _route(c) == c.route and that the restated plan agrees with the library's own answer (synthsr_conv3d_plan) -- the routing half
