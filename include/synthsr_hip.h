@@ -628,6 +628,30 @@ int synthsr_seg_head_dice_bwd(const float* probs, const int32_t* seg, const int3
                               const float* w, const float* sums, float scale, float* dbn, float* dw, float* db,
                               synthsr_stream_t stream);
 
+/* --- segmenting with a trained softmax-headed U-Net, scoring label maps (fp32) ------------------------------------------
+ * x, stats / gamma / beta / eps (inference: the moving statistics), w, b as above; labels [N]: head channel -> label VALUE.
+ * C <= 64 with C % 4 == 0, 2 <= N <= 64 (label_counts: 1 <= N <= 64): anything else returns SYNTHSR_EINVAL before any launch.
+ * argmax:     out[v] = labels[argmax_n(bn(x[v]) . w + b)] (int32), nothing else is written; the argmax is taken on the
+ *             logits, on exactly equal values the lowest channel wins.
+ * tta_argmax: second pass of a flip-averaged prediction.  x is the feature map of the volume flipped along axis 0 of
+ *             shape [3]; prev [nvox][N] the posteriors of the unflipped pass; perm [N] the channel permutation swapping left
+ *             and right structures (identity: 0 .. N-1).  With mirror(v) = voxel v with index 0 reversed,
+ *               p[n] = 0.5 (softmax(bn(x[v]) . w + b)[perm[n]] + prev[mirror(v)][n]),
+ *             out[mirror(v)] = labels[argmax_n p[n]] (lowest channel on ties) and, unless probs_out is NULL,
+ *             probs_out[mirror(v)][n] = p[n].  probs_out may not overlap prev.
+ * label_counts: a, b [nvox] label maps, lut as above; counts [3][N] (zeroed by the caller) accumulate, per class k,
+ *             |a = k and b = k|, |a = k|, |b = k|; values outside the table or mapped to -1 count nowhere.  Integer sums:
+ *             exact and order-independent.  Dice_k = 2 counts[0][k] / (counts[1][k] + counts[2][k]). */
+int synthsr_seg_head_argmax(const float* x, int64_t nvox, int C, const float* stats, const float* gamma, const float* beta,
+                            float eps, const float* w, const float* b, int N, const int32_t* labels, int32_t* out,
+                            synthsr_stream_t stream);
+int synthsr_seg_head_tta_argmax(const float* x, const int* shape, int C, const float* stats, const float* gamma,
+                                const float* beta, float eps, const float* w, const float* b, int N, const int32_t* labels,
+                                const float* prev, const int32_t* perm, int32_t* out, float* probs_out,
+                                synthsr_stream_t stream);
+int synthsr_seg_label_counts(const int32_t* a, const int32_t* b, int64_t nvox, const int32_t* lut, int lut_n, int N,
+                             uint64_t* counts, synthsr_stream_t stream);
+
 /* keras.optimizers.Adam (Keras 2.3.1; SynthSR/training.py:444): lr_t = lr*sqrt(1-b2^t)/(1-b1^t),
  * p -= lr_t*m/(sqrt(v)+eps).  lr already includes the 1/(1+decay*iter) factor. */
 int synthsr_adam_step(float* p, const float* g, float* m, float* v, int64_t n, float lr_t, float beta1,

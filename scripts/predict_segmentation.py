@@ -1,0 +1,88 @@
+#!/usr/bin/env python
+"""Segments volumes with a network trained by scripts/training_segmentation.py and, given ground-truth label maps, scores
+the result with the per-label Dice coefficient.
+
+    python scripts/predict_segmentation.py <path_images> <path_segmentations> --model M.npz|M.h5 --labels L.npy
+                                           [--lr_pairs P.npy] [--posteriors <path>] [--disable_flipping]
+                                           [--n_levels 5 --conv_per_level 2 --unet_feat 24 --feat_mult 2 --activation elu]
+                                           [--truth <path> [--scores S.npy|S.csv]]
+
+<path_images>, <path_segmentations> (and --posteriors, --truth) are all single files or all folders; label maps written
+into a folder carry the suffix _seg.  --labels: the label values in head-channel order (what training_segmentation took as
+segmentation_label_list); --lr_pairs: a [K, 2] array of (left value, right value) pairs whose channels are swapped in the
+flipped pass of the test-time augmentation."""
+import os
+import sys
+from argparse import ArgumentParser
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def build_parser():
+    p = ArgumentParser(description='segmentation with a trained segmentation U-Net (MI355X build)')
+    p.add_argument('path_images', help='scan, or folder of scans, to segment')
+    p.add_argument('path_segmentations', help='output label map (or folder, if path_images is a folder)')
+    p.add_argument('--model', required=True, help='weights: the .npz or .h5 checkpoint of training_segmentation')
+    p.add_argument('--labels', required=True, help='.npy with the label values in head-channel order')
+    p.add_argument('--lr_pairs', default=None, help='.npy [K, 2] of (left value, right value) label pairs')
+    p.add_argument('--posteriors', default=None, help='also write the posteriors: file (or folder)')
+    p.add_argument('--disable_flipping', action='store_true', help='no left-right flip averaging at test time')
+    p.add_argument('--n_levels', type=int, default=5)
+    p.add_argument('--conv_per_level', dest='nb_conv_per_level', type=int, default=2)
+    p.add_argument('--unet_feat', dest='unet_feat_count', type=int, default=24)
+    p.add_argument('--feat_mult', dest='feat_multiplier', type=int, default=2)
+    p.add_argument('--activation', type=str, default='elu')
+    p.add_argument('--truth', default=None, help='ground-truth label map (or folder, sorted like the images): score with Dice')
+    p.add_argument('--scores', default=None, help='write the per-label Dice table here (.npy or .csv); needs --truth')
+    return p
+
+
+def write_scores(path, labels, table):
+    """table [n_volumes, N] -> .npy (the table), or .csv (a header of label values, one row per volume)"""
+    if path.endswith('.npy'):
+        np.save(path, table)
+    elif path.endswith('.csv'):
+        with open(path, 'w') as f:
+            f.write(','.join(str(int(v)) for v in labels) + '\n')
+            for row in table:
+                f.write(','.join(repr(float(v)) for v in row) + '\n')
+    else:
+        raise ValueError('--scores takes a .npy or a .csv path, got %s' % path)
+
+
+def main(argv=None):
+    parser = build_parser()
+    args = parser.parse_args(argv)
+    if args.scores is not None and args.truth is None:
+        parser.error('--scores needs --truth')
+    if args.scores is not None and not args.scores.endswith(('.npy', '.csv')):
+        parser.error('--scores takes a .npy or a .csv path')
+    from synthsr_amd import volumes as V
+    from synthsr_amd.predict_segmentation import predict_segmentation, dice_scores, label_values, mean_dice
+    labels = label_values(args.labels)
+    lr_pairs = None if args.lr_pairs is None else np.load(args.lr_pairs)
+    outs = predict_segmentation(args.path_images, args.path_segmentations, args.model, labels,
+                                path_posteriors=args.posteriors, lr_pairs=lr_pairs, disable_flipping=args.disable_flipping,
+                                n_levels=args.n_levels, nb_conv_per_level=args.nb_conv_per_level,
+                                unet_feat_count=args.unet_feat_count, feat_multiplier=args.feat_multiplier,
+                                activation=args.activation)
+    if args.truth is None:
+        return None
+    truths = V.list_images_in_folder(os.path.abspath(args.truth))
+    if len(truths) != len(outs):
+        raise ValueError('%d ground-truth label maps for %d segmentations' % (len(truths), len(outs)))
+    table = np.stack([dice_scores(o, t, labels) for o, t in zip(outs, truths)])
+    for o, row in zip(outs, table):
+        print(o)
+        for v, d in zip(labels, row):
+            print('  label %5d  Dice %s' % (v, 'absent' if np.isnan(d) else '%.4f' % d))
+        print('  mean Dice %.4f' % mean_dice(row))
+    if args.scores is not None:
+        write_scores(args.scores, labels, table)
+    return table
+
+
+if __name__ == '__main__':
+    main()

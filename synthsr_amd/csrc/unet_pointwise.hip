@@ -1744,6 +1744,189 @@ __global__ __launch_bounds__(256) void seg_head_dice_bwd_kernel(const float* __r
   syn_det_gather_end(N * C + N);
 }
 
+// ------------------------------------------------------------------ softmax head -> label map (inference, fp32)
+// Segmenting with a trained segmentation U-Net: inference-mode BatchNorm, head and argmax over the N classes in one pass, on
+// the tiles, LDS strides and matrix-instruction layout of seg_head_dice_fwd_kernel.  The label VALUE labels[n] of the winning
+// channel is written (int32); on exactly equal values the lowest channel wins (numpy.argmax).
+//   TTA = false: the argmax is taken on the logits (softmax is monotone): no expf, no posteriors anywhere.
+//   TTA = true:  second pass of the flip-averaged prediction, run on the volume flipped along its first axis.  With prev
+//                [nvox][N] the posteriors of the unflipped pass:  p[n] = 0.5 (softmax(logits)[perm[n]] + prev[mirror(v)][n]),
+//                mirror(v) = voxel v with index 0 of [d0][plane] reversed, perm = the channel permutation that swaps left and
+//                right structures (an entry outside [0, N) is read as the identity).  The head's columns are staged in
+//                permuted order, so lane n holds the flipped pass's posterior of channel perm[n] and reads prev in place.
+//                Label and, if probs_out, p are written at mirror(v): the outputs are in the unflipped frame.  probs_out
+//                must not overlap prev.
+// Dynamic LDS (floats): wl [C][SW] | xs [4][16][SX] | scale, shift [64 + 64] | bias [64] | label values [64]
+template <bool TTA>
+__device__ __forceinline__ void shd_label_sweep(const float* __restrict__ x, int64_t nvox, int C,
+                                                const float* __restrict__ stats, const float* __restrict__ gamma,
+                                                const float* __restrict__ beta, float eps, const float* __restrict__ W,
+                                                const float* __restrict__ b, int N, const int32_t* __restrict__ labels,
+                                                const float* __restrict__ prev, const int32_t* __restrict__ perm, int d0,
+                                                int64_t plane, int32_t* __restrict__ out, float* __restrict__ probs_out,
+                                                int SX, int SW) {
+  extern __shared__ float smem[];
+  const int NB = (N + 15) >> 4, C4 = C >> 2;
+  float* wl = smem;
+  float* xs = wl + C * SW;
+  float* ssc = xs + SHD_TILE * SX;
+  float* ssh = ssc + 64;
+  float* sb = ssh + 64;
+  int* slab = reinterpret_cast<int*>(sb + 64);
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, col = lane & 15, quad = lane >> 4;
+  auto column = [&](int n) {  // head column behind channel n (n < N)
+    if (!TTA) return n;
+    const int p = perm[n];
+    return (p >= 0 && p < N) ? p : n;
+  };
+  for (int i = tid; i < C * SW; i += 256) {
+    const int c = i / SW, n = i - c * SW;
+    wl[i] = n < N ? W[c * N + column(n)] : 0.f;
+  }
+  for (int i = tid; i < C; i += 256) bn_coeff(stats, gamma, beta, eps, C, i, ssc[i], ssh[i]);
+  for (int i = tid; i < 64; i += 256) {
+    sb[i] = i < N ? b[column(i)] : 0.f;
+    slab[i] = i < N ? labels[i] : 0;
+  }
+  __syncthreads();
+  float* xw = xs + wave * 16 * SX;
+  for (int64_t base = (int64_t)blockIdx.x * SHD_TILE; base < nvox; base += (int64_t)gridDim.x * SHD_TILE) {
+    const int64_t v0 = base + wave * 16;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {  // BatchNorm output of the wave's 16 voxels (rows past the volume: zeros)
+      const int i = lane + 64 * j;
+      if (i < 16 * C4) {
+        const int r = i / C4, c = (i - r * C4) * 4;
+        float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (v0 + r < nvox) {
+          const float4 a = ld4(x + (v0 + r) * C + c);
+          o = make_float4(fmaf(a.x, ssc[c], ssh[c]), fmaf(a.y, ssc[c + 1], ssh[c + 1]), fmaf(a.z, ssc[c + 2], ssh[c + 2]),
+                          fmaf(a.w, ssc[c + 3], ssh[c + 3]));
+        }
+        *reinterpret_cast<float4*>(xw + r * SX + c) = o;
+      }
+    }
+    __syncthreads();
+    shd_f32x4 acc[4];
+#pragma unroll
+    for (int nb = 0; nb < 4; ++nb) acc[nb] = shd_f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int c0 = 0; c0 < C; c0 += 4) {  // logits [16 voxels][16 classes] per class block, K = channels
+      const float a = xw[col * SX + c0 + quad];
+#pragma unroll
+      for (int nb = 0; nb < 4; ++nb)
+        if (nb < NB) acc[nb] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, wl[(c0 + quad) * SW + nb * 16 + col], acc[nb], 0, 0, 0);
+    }
+    int win = 0;  // lane col < 4 of a quad ends up with the winning channel of voxel 4 quad + col
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {  // voxel 4 quad + r of the wave: its classes sit in the 16 lanes of the quad x NB registers
+      const int64_t v = v0 + 4 * quad + r;
+      float val[4];
+#pragma unroll
+      for (int nb = 0; nb < 4; ++nb) {
+        const int n = nb * 16 + col;
+        val[nb] = (nb < NB && n < N) ? acc[nb][r] + sb[n] : -INFINITY;
+      }
+      if (TTA) {
+        int64_t m = 0;
+        if (v < nvox) m = v + (int64_t)(d0 - 1 - 2 * (int)(v / plane)) * plane;
+        float mx = fmaxf(fmaxf(val[0], val[1]), fmaxf(val[2], val[3]));
+#pragma unroll
+        for (int o = 1; o < 16; o <<= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
+        float den = 0.f;
+#pragma unroll
+        for (int nb = 0; nb < 4; ++nb) {
+          val[nb] = (nb < NB && nb * 16 + col < N) ? expf(val[nb] - mx) : 0.f;
+          den += val[nb];
+        }
+#pragma unroll
+        for (int o = 1; o < 16; o <<= 1) den += __shfl_xor(den, o, 64);
+        const float inv = 1.f / den;
+#pragma unroll
+        for (int nb = 0; nb < 4; ++nb) {
+          const int n = nb * 16 + col;
+          if (nb < NB && n < N && v < nvox) {
+            val[nb] = 0.5f * (val[nb] * inv + prev[m * N + n]);
+            if (probs_out) probs_out[m * N + n] = val[nb];
+          } else {
+            val[nb] = -INFINITY;
+          }
+        }
+      }
+      float bv = -INFINITY;
+      int bi = 64;
+#pragma unroll
+      for (int nb = 0; nb < 4; ++nb)
+        if (val[nb] > bv) {  // ascending channels, strictly greater: the lowest channel of equal values stays
+          bv = val[nb];
+          bi = nb * 16 + col;
+        }
+#pragma unroll
+      for (int o = 1; o < 16; o <<= 1) {
+        const float ov = __shfl_xor(bv, o, 64);
+        const int oi = __shfl_xor(bi, o, 64);
+        if (ov > bv || (ov == bv && oi < bi)) {
+          bv = ov;
+          bi = oi;
+        }
+      }
+      if (col == r) win = bi;
+    }
+    if (col < 4) {
+      const int64_t v = v0 + 4 * quad + col;
+      if (v < nvox) {
+        const int64_t m = TTA ? v + (int64_t)(d0 - 1 - 2 * (int)(v / plane)) * plane : v;
+        out[m] = slab[win < N ? win : 0];  // (no finite value at all: channel 0)
+      }
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void seg_head_argmax_kernel(const float* __restrict__ x, int64_t nvox, int C,
+                                                              const float* __restrict__ stats,
+                                                              const float* __restrict__ gamma,
+                                                              const float* __restrict__ beta, float eps,
+                                                              const float* __restrict__ W, const float* __restrict__ b, int N,
+                                                              const int32_t* __restrict__ labels, int32_t* __restrict__ out,
+                                                              int SX, int SW) {
+  shd_label_sweep<false>(x, nvox, C, stats, gamma, beta, eps, W, b, N, labels, nullptr, nullptr, 1, nvox, out, nullptr, SX, SW);
+}
+
+__global__ __launch_bounds__(256) void seg_head_tta_argmax_kernel(const float* __restrict__ x, int64_t nvox, int C,
+                                                                  const float* __restrict__ stats,
+                                                                  const float* __restrict__ gamma,
+                                                                  const float* __restrict__ beta, float eps,
+                                                                  const float* __restrict__ W, const float* __restrict__ b,
+                                                                  int N, const int32_t* __restrict__ labels,
+                                                                  const float* __restrict__ prev,
+                                                                  const int32_t* __restrict__ perm, int d0, int64_t plane,
+                                                                  int32_t* __restrict__ out, float* __restrict__ probs_out,
+                                                                  int SX, int SW) {
+  shd_label_sweep<true>(x, nvox, C, stats, gamma, beta, eps, W, b, N, labels, prev, perm, d0, plane, out, probs_out, SX, SW);
+}
+
+// Dice counts of two label maps: counts[0][k] += |a = k and b = k|, counts[1][k] += |a = k|, counts[2][k] += |b = k| over the
+// voxels, k = shd_class of the label value (values outside the table or mapped to -1 count nowhere).  Per-workgroup histograms
+// in LDS (integer atomics), one integer atomicAdd flush per workgroup: the sums are exact whatever the order.
+__global__ __launch_bounds__(256) void seg_label_counts_kernel(const int32_t* __restrict__ a, const int32_t* __restrict__ b,
+                                                               int64_t nvox, const int32_t* __restrict__ lut, int lut_n, int N,
+                                                               unsigned long long* __restrict__ counts) {
+  __shared__ unsigned long long h[3 * SEG_MAXN];
+  for (int i = threadIdx.x; i < 3 * SEG_MAXN; i += blockDim.x) h[i] = 0ull;
+  __syncthreads();
+  for (int64_t v = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; v < nvox; v += (int64_t)gridDim.x * blockDim.x) {
+    const int ka = shd_class(a[v], lut, lut_n, N), kb = shd_class(b[v], lut, lut_n, N);
+    if (ka >= 0) atomicAdd(&h[SEG_MAXN + ka], 1ull);
+    if (kb >= 0) atomicAdd(&h[2 * SEG_MAXN + kb], 1ull);
+    if (ka >= 0 && ka == kb) atomicAdd(&h[ka], 1ull);
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < 3 * N; i += blockDim.x) {
+    const int row = i / N, k = i - row * N;
+    const unsigned long long c = h[row * SEG_MAXN + k];
+    if (c) atomicAdd(&counts[i], c);
+  }
+}
+
 // ------------------------------------------------------------------------------------------ Adam (Keras 2.3.1)
 __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                    float* __restrict__ m, float* __restrict__ v, int64_t n, float lr_t,
@@ -2404,6 +2587,51 @@ int synthsr_seg_head_dice_bwd(const float* probs, const int32_t* seg, const int3
   const size_t smem = ((size_t)NB * 16 * SW + (size_t)SHD_TILE * (SN + SX) + 5 * 64) * sizeof(float);
   hipLaunchKernelGGL(seg_head_dice_bwd_kernel, dim3(syn_grid(nvox, SHD_TILE, head_grid())), dim3(256), smem, (hipStream_t)stream,
                      probs, seg, lut, lut_n, x, nvox, C, N, stats, gamma, beta, eps, w, sums, scale, dbn, dw, db, SX, SN, SW);
+  SYN_CHECK_LAUNCH();
+  return SYNTHSR_OK;
+}
+
+// the two label-map kernels: the limits of the Dice head, at least two classes
+static bool shd_label_ok(int64_t nvox, int C, int N, const void* x) { return N >= 2 && shd_ok(nvox, C, N, 1, x); }
+static size_t shd_label_smem(int C, int N) {  // <= 35 KB
+  return ((size_t)C * shd_stride((N + 15) / 16) + (size_t)SHD_TILE * shd_stride((C + 15) / 16) + 4 * 64) * sizeof(float);
+}
+
+int synthsr_seg_head_argmax(const float* x, int64_t nvox, int C, const float* stats, const float* gamma, const float* beta,
+                            float eps, const float* w, const float* b, int N, const int32_t* labels, int32_t* out,
+                            synthsr_stream_t stream) {
+  if (!x || !stats || !gamma || !beta || !w || !b || !labels || !out || !shd_label_ok(nvox, C, N, x)) return SYNTHSR_EINVAL;
+  hipLaunchKernelGGL(seg_head_argmax_kernel, dim3(syn_grid(nvox, SHD_TILE, head_grid())), dim3(256), shd_label_smem(C, N),
+                     (hipStream_t)stream, x, nvox, C, stats, gamma, beta, eps, w, b, N, labels, out,
+                     shd_stride((C + 15) / 16), shd_stride((N + 15) / 16));
+  SYN_CHECK_LAUNCH();
+  return SYNTHSR_OK;
+}
+
+int synthsr_seg_head_tta_argmax(const float* x, const int* shape, int C, const float* stats, const float* gamma,
+                                const float* beta, float eps, const float* w, const float* b, int N, const int32_t* labels,
+                                const float* prev, const int32_t* perm, int32_t* out, float* probs_out,
+                                synthsr_stream_t stream) {
+  if (!shape || shape[0] < 1 || shape[1] < 1 || shape[2] < 1) return SYNTHSR_EINVAL;
+  const int64_t plane = (int64_t)shape[1] * shape[2], nvox = plane * shape[0];
+  if (!x || !stats || !gamma || !beta || !w || !b || !labels || !prev || !perm || !out || !shd_label_ok(nvox, C, N, x))
+    return SYNTHSR_EINVAL;
+  if (probs_out) {  // written at the mirrored voxel while other workgroups still read prev: the two may not share memory
+    const uintptr_t p0 = (uintptr_t)prev, q0 = (uintptr_t)probs_out, bytes = (uintptr_t)nvox * N * sizeof(float);
+    if (p0 < q0 + bytes && q0 < p0 + bytes) return SYNTHSR_EINVAL;
+  }
+  hipLaunchKernelGGL(seg_head_tta_argmax_kernel, dim3(syn_grid(nvox, SHD_TILE, head_grid())), dim3(256), shd_label_smem(C, N),
+                     (hipStream_t)stream, x, nvox, C, stats, gamma, beta, eps, w, b, N, labels, prev, perm, shape[0], plane, out,
+                     probs_out, shd_stride((C + 15) / 16), shd_stride((N + 15) / 16));
+  SYN_CHECK_LAUNCH();
+  return SYNTHSR_OK;
+}
+
+int synthsr_seg_label_counts(const int32_t* a, const int32_t* b, int64_t nvox, const int32_t* lut, int lut_n, int N,
+                             uint64_t* counts, synthsr_stream_t stream) {
+  if (!a || !b || !lut || !counts || nvox < 1 || lut_n < 1 || N < 1 || N > SEG_MAXN) return SYNTHSR_EINVAL;
+  hipLaunchKernelGGL(seg_label_counts_kernel, dim3(syn_grid(nvox, 256, head_grid())), dim3(256), 0, (hipStream_t)stream, a, b,
+                     nvox, lut, lut_n, N, reinterpret_cast<unsigned long long*>(counts));
   SYN_CHECK_LAUNCH();
   return SYNTHSR_OK;
 }

@@ -862,6 +862,71 @@ def seg_head_dice_bwd(probs, seg, lut, x, stats, gamma, beta, w, sums, dbn, dw, 
     return dbn
 
 
+def _seg_head_label_args(what, x, w, b, labels, out):
+    """shared checks of seg_head_argmax / _tta_argmax: float32 activations and head, int32 label values and label map"""
+    if x.dim() != 4:
+        raise ValueError('x should be [d0, d1, d2, C]')
+    C = int(x.shape[-1])
+    nvox = x.numel() // C
+    N = w.numel() // C
+    if w.numel() != C * N or N < 2 or b.numel() != N or labels.numel() != N or out.numel() != nvox:
+        raise ValueError('%s: head [%d, %d] with a bias of %d, %d label values and a label map of %d values do not fit %d voxels'
+                         % (what, C, N, b.numel(), labels.numel(), out.numel(), nvox))
+    if x.dtype != torch.float32 or w.dtype != torch.float32 or b.dtype != torch.float32:
+        raise ValueError('%s is fp32 only (x is %s)' % (what, x.dtype))
+    if labels.dtype != torch.int32 or out.dtype != torch.int32:
+        raise ValueError('%s takes the label values and writes the label map as int32 (got %s, %s)'
+                         % (what, labels.dtype, out.dtype))
+    return C, nvox, N
+
+
+def seg_head_argmax(x, stats, gamma, beta, w, b, labels, out, eps=BN_EPS):
+    """out [nvox] (int32) = labels[argmax_n(bn(x) @ w + b)]: the label map of a softmax head without its posteriors (the
+    argmax is taken on the logits; equal values: the lowest channel).  x [d0,d1,d2,C] with C <= 64, 2 <= N <= 64; labels
+    [N] int32: head channel -> label value"""
+    C, nvox, N = _seg_head_label_args('seg_head_argmax', x, w, b, labels, out)
+    _lib.check(_L().synthsr_seg_head_argmax(_lib.ptr(x), nvox, C, _lib.ptr(stats), _lib.ptr(gamma), _lib.ptr(beta), eps,
+                                            _lib.ptr(w), _lib.ptr(b), N, _lib.ptr(labels), _lib.ptr(out), _lib.stream()),
+               'seg_head_argmax')
+    return out
+
+
+def seg_head_tta_argmax(x, stats, gamma, beta, w, b, labels, prev, perm, out, probs_out=None, eps=BN_EPS):
+    """second pass of a flip-averaged segmentation: x [d0,d1,d2,C] is the feature map of the volume flipped along axis 0,
+    prev [nvox, N] the posteriors of the unflipped pass, perm [N] int32 the channel permutation swapping left and right
+    labels.  p = 0.5 (softmax(bn(x) @ w + b)[perm] + prev[mirrored voxel]); out [nvox] (int32) <- labels[argmax p] and
+    probs_out [nvox, N] (optional, not prev) <- p, both at the mirrored voxel: in the frame of the unflipped volume"""
+    C, nvox, N = _seg_head_label_args('seg_head_tta_argmax', x, w, b, labels, out)
+    if prev.numel() != nvox * N or perm.numel() != N or (probs_out is not None and probs_out.numel() != nvox * N):
+        raise ValueError('seg_head_tta_argmax: posteriors [%d, %d] and a permutation of %d channels are needed' % (nvox, N, N))
+    if prev.dtype != torch.float32 or perm.dtype != torch.int32 or (probs_out is not None and probs_out.dtype != torch.float32):
+        raise ValueError('seg_head_tta_argmax takes float32 posteriors and an int32 permutation')
+    _lib.check(_L().synthsr_seg_head_tta_argmax(_lib.ptr(x), _lib.i3(x.shape[:3]), C, _lib.ptr(stats), _lib.ptr(gamma),
+                                                _lib.ptr(beta), eps, _lib.ptr(w), _lib.ptr(b), N, _lib.ptr(labels),
+                                                _lib.ptr(prev), _lib.ptr(perm), _lib.ptr(out), _lib.ptr(probs_out),
+                                                _lib.stream()), 'seg_head_tta_argmax')
+    return out
+
+
+def seg_label_counts(a, b, lut, N, counts=None):
+    """counts [3, N] (int64, zeroed here) <- per head channel k: voxels with a = b = k | with a = k | with b = k, for two int32
+    label maps of equal size; lut (int32): label value -> channel or -1 (values outside the table: no channel).  Exact."""
+    if a.dtype != torch.int32 or b.dtype != torch.int32 or lut.dtype != torch.int32:
+        raise ValueError('seg_label_counts takes the label maps and the lookup table as int32 (got %s, %s, %s)'
+                         % (a.dtype, b.dtype, lut.dtype))
+    if a.numel() != b.numel() or a.numel() < 1 or lut.numel() < 1:
+        raise ValueError('seg_label_counts: label maps of %d and %d voxels' % (a.numel(), b.numel()))
+    N = int(N)
+    if counts is None:
+        counts = torch.empty(3, N, dtype=torch.int64, device=a.device)
+    if counts.numel() != 3 * N or counts.dtype != torch.int64:
+        raise ValueError('seg_label_counts: counts should be int64 [3, %d]' % N)
+    counts.zero_()
+    _lib.check(_L().synthsr_seg_label_counts(_lib.ptr(a), _lib.ptr(b), a.numel(), _lib.ptr(lut), int(lut.numel()), N,
+                                             _lib.ptr(counts), _lib.stream()), 'seg_label_counts')
+    return counts
+
+
 def adam_step(p, g, m, v, lr_t, beta1=0.9, beta2=0.999, eps=1e-7, grad_scale=1.0):
     lib = _L()
     _lib.check(lib.synthsr_adam_step(_lib.ptr(p), _lib.ptr(g), _lib.ptr(m), _lib.ptr(v), p.numel(), float(lr_t),

@@ -1,0 +1,238 @@
+"""Segmenting volumes with a network trained by `synthsr_amd.segmentation_training.training_segmentation`, and scoring label
+maps with the Dice coefficient.
+
+    per volume:  resample to 1 mm, re-orient to RAS, min-max normalise, zero-pad to a multiple of 32 (predict.prepare_volume:
+                 the image the segmentation network saw in training is a clean one-channel image) -> U-Net forward with the
+                 moving statistics -> head + argmax in one kernel (UNet3D.predict_labels) -> crop -> int32 label map.
+
+With flip averaging the first pass keeps its posteriors (UNet3D.predict_probs); the second pass, on the volume flipped along
+its first (left-right) axis, averages them with its own mirrored ones -- channels of left and right structures swapped --
+inside the head kernel and writes the label map of the average.  Without it no posterior is ever formed.
+
+The head's channel order is `segmentation_label_list`, as in training_segmentation().  fp32 only."""
+import os
+import numpy as np
+
+from . import host_math as hm
+from . import volumes as V
+from .predict import prepare_volume
+from .segmentation_training import segmentation_lut
+
+
+def label_values(segmentation_label_list):
+    """the label values in head-channel order as int32 (the checks of segmentation_lut: non-negative integers, none twice)"""
+    segmentation_lut(segmentation_label_list)
+    return np.asarray(hm.load_array_if_path(segmentation_label_list)).reshape(-1).astype(np.int32)
+
+
+def lr_permutation(segmentation_label_list, lr_pairs=None):
+    """int32 [N]: head channel -> the channel of the same structure on the other side.  lr_pairs: (left value, right value)
+    pairs of listed label values, no value in more than one place; channels of unpaired labels map to themselves."""
+    labels = label_values(segmentation_label_list)
+    perm = np.arange(len(labels), dtype=np.int32)
+    if lr_pairs is None:
+        return perm
+    pairs = np.asarray(lr_pairs)
+    if pairs.size == 0:
+        return perm
+    if pairs.ndim != 2 or pairs.shape[1] != 2:
+        raise ValueError('lr_pairs should be a list of (left value, right value) pairs, got an array of shape %s'
+                         % (pairs.shape,))
+    if np.any(pairs != np.round(pairs)):
+        raise ValueError('lr_pairs should hold integer label values')
+    pairs = pairs.astype(np.int64)
+    flat = pairs.reshape(-1)
+    if len(np.unique(flat)) != len(flat):
+        raise ValueError('lr_pairs names a label value twice')
+    channel = {int(v): i for i, v in enumerate(labels)}
+    unlisted = [int(v) for v in flat if int(v) not in channel]
+    if unlisted:
+        raise ValueError('lr_pairs names label values that are not in the segmentation label list: %s' % unlisted)
+    for left, right in pairs:
+        perm[channel[int(left)]], perm[channel[int(right)]] = channel[int(right)], channel[int(left)]
+    return perm
+
+
+def dice_from_counts(counts):
+    """per-label Dice 2 |a = k and b = k| / (|a = k| + |b = k|) as float64 from counts [3, N] (overlap, |a|, |b|); a label
+    absent from both maps scores NaN"""
+    counts = np.asarray(counts)
+    if counts.ndim != 2 or counts.shape[0] != 3:
+        raise ValueError('counts should be [3, N], got %s' % (counts.shape,))
+    top = 2.0 * counts[0].astype(np.float64)
+    bottom = counts[1].astype(np.float64) + counts[2].astype(np.float64)
+    out = np.full(counts.shape[1], np.nan, dtype=np.float64)
+    np.divide(top, bottom, out=out, where=bottom > 0)
+    return out
+
+
+def mean_dice(scores):
+    """mean over the labels present in at least one of the two maps (NaN when there is none)"""
+    scores = np.asarray(scores, dtype=np.float64)
+    present = ~np.isnan(scores)
+    return float(scores[present].mean()) if present.any() else float('nan')
+
+
+def check_head_width(state, table, labels):
+    """the weight file's head should have one channel per listed label"""
+    name = table.head['w']
+    if name in state:
+        width = int(np.shape(state[name])[-1])
+        if width != len(labels):
+            raise ValueError('the network\'s head has %d channels, the segmentation label list %d labels' % (width, len(labels)))
+
+
+class SegmentationPredictor:
+    """The softmax-headed U-Net of training_segmentation() (one input channel), rebuilt per padded volume shape like
+    predict.Predictor; one resident network."""
+
+    def __init__(self, path_model, segmentation_label_list, n_levels=5, nb_conv_per_level=2, unet_feat_count=24,
+                 feat_multiplier=2, activation='elu', device=None, state_dict=None):
+        self.labels = label_values(segmentation_label_list)
+        self.lut = segmentation_lut(self.labels)
+        self.arch = dict(nb_features=unet_feat_count, nb_levels=n_levels, conv_size=3, nb_labels=len(self.labels),
+                         feat_mult=feat_multiplier, nb_conv_per_level=nb_conv_per_level, batch_norm=-1,
+                         final_pred_activation='softmax', activation=activation)
+        self.device = device or 'cuda'
+        self.state = state_dict
+        if state_dict is None:
+            if path_model is None or not os.path.isfile(path_model):
+                raise FileNotFoundError('model file %s not found (the .npz or .h5 checkpoint written by '
+                                        'training_segmentation)' % path_model)
+            from .training import read_weights
+            self.state = {k: v for k, v in read_weights(path_model).items() if not k.startswith('optimizer/')}
+        from .unet import UNet3D
+        side = 2 ** (int(n_levels) - 1)
+        check_head_width(self.state, UNet3D(input_shape=[side] * 3 + [1], table_only=True, **self.arch), self.labels)
+        self.nets = {}
+        self._labels_dev = None
+
+    def net_for(self, shape):
+        import torch
+        from .unet import unet
+        key = tuple(int(s) for s in shape)
+        if key not in self.nets:
+            self.nets.clear()  # one resident network: volumes of a folder usually share their shape
+            net = unet(input_shape=list(key) + [1], conv_dropout=0, input_model=None, device=self.device, **self.arch)
+            # a weight file with another layer prefix / missing layers must not leave random weights in place silently
+            missing = [nm for nm, _, _ in net.specs if nm not in self.state]
+            missing += [b['name'] + '/moving_mean' for b in net.bn_layers if b['name'] + '/moving_mean' not in self.state]
+            if missing:
+                raise KeyError('the weight file lacks %d of the network\'s tensors (first: %s): wrong model file or layer '
+                               'prefix?' % (len(missing), missing[0]))
+            net.load_state_dict({k: torch.as_tensor(np.ascontiguousarray(v)) for k, v in self.state.items()}, strict=True)
+            net.repack()
+            self.nets[key] = net
+        return self.nets[key]
+
+    def segment_volume(self, S, flipping=True, lr_pairs=None, return_posteriors=False):
+        """S [W0,W1,W2] (numpy, padded: every side a multiple of 2**(n_levels-1)) -> int32 label map [W0,W1,W2] of label
+        values (numpy); with return_posteriors also the posteriors [W0,W1,W2,N] float32 the map is the argmax of.
+        flipping: average with the pass on the volume flipped along the first (left-right) axis, the channels of each
+        (left value, right value) pair of lr_pairs swapped."""
+        import torch
+        perm = lr_permutation(self.labels, lr_pairs)
+        S = np.asarray(S)
+        if S.ndim != 3:
+            raise ValueError('segment_volume takes one 3-D volume, got an array of shape %s' % (S.shape,))
+        net = self.net_for(S.shape)
+        N = len(self.labels)
+        if self._labels_dev is None:
+            self._labels_dev = torch.from_numpy(self.labels).to(net.device)
+        x = torch.from_numpy(np.ascontiguousarray(S, dtype=np.float32)).to(net.device)[..., None].contiguous()
+        probs = None
+        if flipping:
+            prev = net.predict_probs(x)
+            out = net.predict_labels(torch.flip(x, dims=[0]).contiguous(), self._labels_dev, prev=prev,
+                                     perm=torch.from_numpy(perm).to(net.device), want_probs=return_posteriors)
+            if return_posteriors:
+                out, probs = out
+        elif return_posteriors:   # the posteriors are asked for: the label map is their argmax (first of equal values)
+            probs = net.predict_probs(x)
+            out = self._labels_dev[torch.argmax(probs, dim=1)]
+        else:
+            out = net.predict_labels(x, self._labels_dev)
+        seg = out.reshape(S.shape).cpu().numpy().astype(np.int32, copy=False)
+        if return_posteriors:
+            return seg, probs.reshape(*S.shape, N).cpu().numpy()
+        return seg
+
+
+def _suffixed(path, suffix):
+    for ext in ('.nii.gz', '.nii', '.mgz', '.npz'):
+        if path.endswith(ext):
+            return path[:-len(ext)] + suffix + ext
+    return path + suffix
+
+
+def predict_segmentation(path_images, path_segmentations, path_model, segmentation_label_list, path_posteriors=None,
+                         lr_pairs=None, disable_flipping=False, n_levels=5, nb_conv_per_level=2, unet_feat_count=24,
+                         feat_multiplier=2, activation='elu', device=None, verbose=True, predictor=None):
+    """The file / folder contract of predict.predict(): `path_images` / `path_segmentations` (and `path_posteriors`, if
+    given) are all single files (.nii, .nii.gz, .mgz, .npz) or all folders; in folders the outputs carry the suffixes
+    `_seg` and `_posteriors`.  Label maps are saved as int32 in the 1 mm RAS frame predict() writes in.  Returns the paths
+    of the label maps."""
+    if 32 % (2 ** (int(n_levels) - 1)) != 0:
+        raise ValueError('volumes are padded to multiples of 32: n_levels = %d needs sides divisible by %d'
+                         % (n_levels, 2 ** (int(n_levels) - 1)))
+    path_images = os.path.abspath(path_images)
+    basename = os.path.basename(path_images)
+    path_segmentations = os.path.abspath(path_segmentations)
+    if not any(ext in basename for ext in ('.nii.gz', '.nii', '.mgz', '.npz')):
+        if os.path.isfile(path_images):
+            raise Exception('extension not supported for %s, only use: nii.gz, .nii, .mgz, or .npz' % path_images)
+        images = V.list_images_in_folder(path_images)
+        os.makedirs(path_segmentations, exist_ok=True)
+        outs = [_suffixed(os.path.join(path_segmentations, os.path.basename(p)), '_seg') for p in images]
+        posts = [None] * len(images)
+        if path_posteriors is not None:
+            os.makedirs(path_posteriors, exist_ok=True)
+            posts = [_suffixed(os.path.join(os.path.abspath(path_posteriors), os.path.basename(p)), '_posteriors')
+                     for p in images]
+    else:
+        assert os.path.isfile(path_images), "files does not exist: %s " \
+                                            "\nplease make sure the path and the extension are correct" % path_images
+        images, outs = [path_images], [path_segmentations]
+        posts = [None if path_posteriors is None else os.path.abspath(path_posteriors)]
+    predictor = predictor or SegmentationPredictor(path_model, segmentation_label_list, n_levels, nb_conv_per_level,
+                                                   unet_feat_count, feat_multiplier, activation, device)
+    if verbose:
+        print('Found %d images' % len(images))
+    for i, (pin, pout, ppost) in enumerate(zip(images, outs, posts)):
+        if verbose:
+            print('  Working on image %d ' % (i + 1))
+            print('  ' + pin)
+        im, aff, _ = V.load_volume(pin, im_only=False, dtype='float')
+        S, idx, shape, aff2 = prepare_volume(im, aff)
+        crop = tuple(slice(int(o), int(o) + int(n)) for o, n in zip(idx, shape))
+        res = predictor.segment_volume(S, flipping=not disable_flipping, lr_pairs=lr_pairs,
+                                       return_posteriors=ppost is not None)
+        seg = res[0] if ppost is not None else res
+        V.save_volume(np.ascontiguousarray(seg[crop]), aff2, None, pout, dtype='int32')
+        if ppost is not None:
+            V.save_volume(np.ascontiguousarray(res[1][crop]), aff2, None, ppost, dtype='float32', n_dims=3)
+    return outs
+
+
+def _label_map(m):
+    if isinstance(m, str):
+        m = V.load_volume(m, im_only=True, dtype='int')
+    m = np.asarray(m)
+    if not np.issubdtype(m.dtype, np.integer):
+        m = np.round(m)
+    return np.ascontiguousarray(m, dtype=np.int32)
+
+
+def dice_scores(seg, truth, label_list, device=None):
+    """per-label Dice (float64 [N], in the order of `label_list`) of two label maps of equal shape, given as arrays or
+    paths; the voxels are counted on the GPU (ops.seg_label_counts).  A label absent from both maps scores NaN."""
+    import torch
+    from . import ops
+    lut = segmentation_lut(label_list)
+    a, b = _label_map(seg), _label_map(truth)
+    if a.shape != b.shape:
+        raise ValueError('dice_scores: label maps of shapes %s and %s' % (a.shape, b.shape))
+    dev = device or 'cuda'
+    counts = ops.seg_label_counts(torch.from_numpy(a).to(dev).reshape(-1), torch.from_numpy(b).to(dev).reshape(-1),
+                                  torch.from_numpy(lut).to(dev), int((lut >= 0).sum()))
+    return dice_from_counts(counts.cpu().numpy())

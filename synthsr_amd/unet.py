@@ -353,7 +353,8 @@ class UNet3D:
         self.repack()
 
     # ------------------------------------------------------------------ buffers
-    _F32_BUFS = ('loss', 'dpred', 'pred', 'loss_unused', 'zero_t', 'probs', 'dwc', 'head_ab', 'dice_sums')
+    _F32_BUFS = ('loss', 'dpred', 'pred', 'loss_unused', 'zero_t', 'probs', 'dwc', 'head_ab', 'dice_sums', 'probs_avg',
+                 'label_map')
 
     def buf(self, key, shape):
         """persistent scratch tensor: activations / activation gradients in the network's dtype, the head's outputs,
@@ -778,6 +779,46 @@ class UNet3D:
         ops.seg_head_fwd(low, self._stats(bn), self.view(bn['gamma']), self.view(bn['beta']), self.view(self.head['w']),
                          self.view(self.head['b']), probs)
         return probs
+
+    def predict_labels(self, x, labels, prev=None, perm=None, want_probs=False):
+        """segmentation with a softmax head: inference forward (moving statistics) of x [d0,d1,d2,Cin] + head + argmax in one
+        kernel -> int32 label map [d0,d1,d2] of the label VALUES labels[channel] (int32 [nb_labels], device); no posteriors
+        are formed.  With prev [nvox, nb_labels] (the posteriors predict_probs returned for the unflipped volume) x is taken
+        as that volume flipped along axis 0: the label map is the argmax of 0.5 (posteriors of x mirrored back, their
+        channels permuted by perm (int32 [nb_labels], None: identity) + prev), in the unflipped frame; want_probs: the
+        averaged posteriors [nvox, nb_labels] are returned as well.  Buffers of the network: valid until its next call."""
+        if self.final_pred_activation != 'softmax':
+            raise ValueError('predict_labels() is for softmax heads; use predict() for a linear head')
+        if self.bf16:
+            raise NotImplementedError('the segmentation head kernels are fp32 only (dtype=%r)' % 'bf16')
+        if self.batch != 1:
+            raise NotImplementedError('predict_labels() takes one volume per call (batch = %d)' % self.batch)
+        if want_probs and prev is None:
+            raise ValueError('predict_labels() forms posteriors only when averaging with prev; use predict_probs()')
+        N = self.nb_labels
+        self._dice = None   # the kept activations are overwritten: backward() needs a new loss_dice()
+        was = self.training
+        self.training = False
+        self.frozen_batch_stats = False
+        try:
+            low, bn = self.forward(x)
+            nvox = low.numel() // low.shape[3]
+            out = self.buf('label_map', [nvox]).view(torch.int32)
+            head = (low, self._stats(bn), self.view(bn['gamma']), self.view(bn['beta']), self.view(self.head['w']),
+                    self.view(self.head['b']), labels)
+            probs = None
+            if prev is None:
+                ops.seg_head_argmax(*head, out)
+            else:
+                if perm is None:
+                    perm = torch.arange(N, dtype=torch.int32, device=self.device)
+                if want_probs:
+                    probs = self.buf('probs_avg', [nvox, N])
+                ops.seg_head_tta_argmax(*head, prev, perm, out, probs)
+        finally:
+            self.training = was
+        out = out.view(*low.shape[:3])
+        return (out, probs) if want_probs else out
 
     def backward_input(self, dbn):
         """gradient w.r.t. the network input of a loss whose gradient w.r.t. the LAST BatchNorm output is `dbn`
