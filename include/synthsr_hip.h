@@ -652,6 +652,27 @@ int synthsr_seg_head_tta_argmax(const float* x, const int* shape, int C, const f
 int synthsr_seg_label_counts(const int32_t* a, const int32_t* b, int64_t nvox, const int32_t* lut, int lut_n, int N,
                              uint64_t* counts, synthsr_stream_t stream);
 
+/* --- a frozen or inference softmax-headed U-Net in bf16 ------------------------------------------------------------------
+ * The feature map x [nvox][C] is bf16 (8-byte aligned: one channel quad per vector load); BatchNorm statistics, gamma / beta,
+ * the head's fp32 master weights w / b, posteriors, prev and the Dice sums stay fp32, so the arithmetic on a given bf16 x is
+ * that of the fp32 entry points above.  Limits as there (C <= 64 with C % 4 == 0, N <= 64; argmax: N >= 2); anything else, a
+ * misaligned x included, returns SYNTHSR_EINVAL before any launch.
+ * seg_head_fwd_bf16: probs [nvox][N] (fp32) = softmax_n(bn(x[v]) . w + b).
+ * seg_head_argmax_bf16 / seg_head_tta_argmax_bf16: synthsr_seg_head_argmax / _tta_argmax on a bf16 x.
+ * seg_dice_bwd_bf16: synthsr_seg_dice_bwd with dbn [nvox][C] stored as bf16 (round to nearest even). */
+int synthsr_seg_head_fwd_bf16(const void* x, int64_t nvox, int C, const float* stats, const float* gamma, const float* beta,
+                              float eps, const float* w, const float* b, int N, float* probs, synthsr_stream_t stream);
+int synthsr_seg_head_argmax_bf16(const void* x, int64_t nvox, int C, const float* stats, const float* gamma,
+                                 const float* beta, float eps, const float* w, const float* b, int N, const int32_t* labels,
+                                 int32_t* out, synthsr_stream_t stream);
+int synthsr_seg_head_tta_argmax_bf16(const void* x, const int* shape, int C, const float* stats, const float* gamma,
+                                     const float* beta, float eps, const float* w, const float* b, int N,
+                                     const int32_t* labels, const float* prev, const int32_t* perm, int32_t* out,
+                                     float* probs_out, synthsr_stream_t stream);
+int synthsr_seg_dice_bwd_bf16(const float* probs, const int32_t* seg, int64_t nvox, int C, int N, const float* w,
+                              const int32_t* cls_idx, const int32_t* cls_gt, int K, const float* sums, float scale, void* dbn,
+                              synthsr_stream_t stream);
+
 /* keras.optimizers.Adam (Keras 2.3.1; SynthSR/training.py:444): lr_t = lr*sqrt(1-b2^t)/(1-b1^t),
  * p -= lr_t*m/(sqrt(v)+eps).  lr already includes the 1/(1+decay*iter) factor. */
 int synthsr_adam_step(float* p, const float* g, float* m, float* v, int64_t n, float lr_t, float beta1,

@@ -5,6 +5,7 @@ the result with the per-label Dice coefficient.
     python scripts/predict_segmentation.py <path_images> <path_segmentations> --model M.npz|M.h5 --labels L.npy
                                            [--lr_pairs P.npy] [--posteriors <path>] [--disable_flipping]
                                            [--n_levels 5 --conv_per_level 2 --unet_feat 24 --feat_mult 2 --activation elu]
+                                           [--dtype f32|bf16]
                                            [--truth <path> [--scores S.npy|S.csv]]
 
 <path_images>, <path_segmentations> (and --posteriors, --truth) are all single files or all folders; label maps written
@@ -34,6 +35,8 @@ def build_parser():
     p.add_argument('--unet_feat', dest='unet_feat_count', type=int, default=24)
     p.add_argument('--feat_mult', dest='feat_multiplier', type=int, default=2)
     p.add_argument('--activation', type=str, default='elu')
+    p.add_argument('--dtype', choices=('f32', 'bf16'), default='f32',
+                   help='arithmetic of the network: bf16 = bf16 activations and packed weights, fp32 head and posteriors')
     p.add_argument('--truth', default=None, help='ground-truth label map (or folder, sorted like the images): score with Dice')
     p.add_argument('--scores', default=None, help='write the per-label Dice table here (.npy or .csv); needs --truth')
     return p
@@ -67,7 +70,7 @@ def main(argv=None):
                                 path_posteriors=args.posteriors, lr_pairs=lr_pairs, disable_flipping=args.disable_flipping,
                                 n_levels=args.n_levels, nb_conv_per_level=args.nb_conv_per_level,
                                 unet_feat_count=args.unet_feat_count, feat_multiplier=args.feat_multiplier,
-                                activation=args.activation)
+                                activation=args.activation, dtype=args.dtype)
     if args.truth is None:
         return None
     truths = V.list_images_in_folder(os.path.abspath(args.truth))

@@ -47,7 +47,7 @@ VALUED = [
 SWITCHES = [('no_flipping', 'flipping', False), ('no_reg_error', 'simulate_registration_error', False),
             ('downsample', 'downsample', True), ('no_rel_map', 'build_reliability_maps', False)]
 # additional flags of this build (parameters of training() the reference's script does not expose)
-EXTRA_VALUED = [('padding_margin', None, int, None), ('seed', None, int, 0)]
+EXTRA_VALUED = [('padding_margin', None, int, None), ('seed', None, int, 0), ('segnet_dtype', None, str, None)]
 EXTRA_SWITCHES = [('no_FS_sort', 'FS_sort', False), ('randomise_res', 'randomise_res', True),
                   ('fs_header_segnet', 'fs_header_segnet', True)]
 

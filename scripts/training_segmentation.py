@@ -16,7 +16,7 @@ import training as _t  # noqa: E402  (scripts/training.py: the flag tables)
 POSITIONAL = _t.POSITIONAL + ('segmentation_label_list',)
 # the flags of scripts/training.py that training_segmentation() has a parameter for
 DROPPED = ('images_dir', 'regression_metric', 'work_with_residual_channel', 'loss_cropping', 'segmentation_model_file',
-           'segmentation_label_list', 'segmentation_label_equivalency', 'relative_weight_segmentation')
+           'segmentation_label_list', 'segmentation_label_equivalency', 'relative_weight_segmentation', 'segnet_dtype')
 VALUED = [row for row in _t.VALUED + _t.EXTRA_VALUED if (row[1] or row[0]) not in DROPPED]
 SWITCHES = [row for row in _t.SWITCHES + _t.EXTRA_SWITCHES if row[1] != 'fs_header_segnet']
 

@@ -146,6 +146,11 @@ SIGNATURES = {
     'synthsr_seg_head_tta_argmax': (c_int, [_P, POINTER(c_int), c_int, _P, _P, _P, c_float, _P, _P, c_int, _P, _P, _P, _P, _P,
                                             _S]),
     'synthsr_seg_label_counts': (c_int, [_P, _P, c_int64, _P, c_int, c_int, _P, _S]),
+    'synthsr_seg_head_fwd_bf16': (c_int, [_P, c_int64, c_int, _P, _P, _P, c_float, _P, _P, c_int, _P, _S]),
+    'synthsr_seg_dice_bwd_bf16': (c_int, [_P, _P, c_int64, c_int, c_int, _P, _P, _P, c_int, _P, c_float, _P, _S]),
+    'synthsr_seg_head_argmax_bf16': (c_int, [_P, c_int64, c_int, _P, _P, _P, c_float, _P, _P, c_int, _P, _P, _S]),
+    'synthsr_seg_head_tta_argmax_bf16': (c_int, [_P, POINTER(c_int), c_int, _P, _P, _P, c_float, _P, _P, c_int, _P, _P, _P, _P,
+                                                 _P, _S]),
     'synthsr_head_bwd': (c_int, [_P, _P, c_int64, c_int, _P, _P, _P, c_float, _P, _P, _P, _P, _S]),
     'synthsr_adam_step': (c_int, [_P, _P, _P, _P, c_int64, c_float, c_float, c_float, c_float, c_float, _S]),
 }

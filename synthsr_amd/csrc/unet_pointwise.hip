@@ -58,6 +58,8 @@ __device__ __forceinline__ void st4(bf16_t* p, float4 v) {
   u.y = f2bf(v.z) | (f2bf(v.w) << 16);
   *reinterpret_cast<uint2*>(p) = u;
 }
+__device__ __forceinline__ void st1(float* p, float v) { *p = v; }
+__device__ __forceinline__ void st1(bf16_t* p, float v) { p->v = (uint16_t)f2bf(v); }
 
 // block-level channel reduction of NV float4 partials held by threads with a fixed channel group
 template <int NV>
@@ -1383,12 +1385,14 @@ __global__ __launch_bounds__(256) void seg_dice_sums_kernel(const float* __restr
 //   dpred_k = -scale/K * (2 gt_k (B_k+e) - 2 pred_k (T_k+e)) / (B_k+e)^2
 //   dlogit_n = p_n (dprob_n - S),  dprob_n = dpred_{class(n)} (0 for labels without class),  S = sum_k dpred_k pred_k
 //   dbn[v][c] = sum_n W[c][n] dlogit_n  = sum_k dpred_k sum_j W[c][idx_kj] p_idx_kj  -  S sum_n W[c][n] p_n
+// T = the element type of dbn (float | bf16_t: the frozen network runs in bf16, one rounding to nearest even at the store)
+template <typename T>
 __global__ __launch_bounds__(256) void seg_dice_bwd_kernel(const float* __restrict__ probs, const int32_t* __restrict__ seg,
                                                            int64_t nvox, int C, int N, const float* __restrict__ W,
                                                            const int32_t* __restrict__ cls_idx,
                                                            const int32_t* __restrict__ cls_gt, int K,
                                                            const float* __restrict__ sums, float scale,
-                                                           float* __restrict__ dbn) {
+                                                           T* __restrict__ dbn) {
   __shared__ float sw[SEG_MAXC * SEG_MAXN], sT[SEG_MAXK], sB[SEG_MAXK];
   __shared__ int sidx[3 * SEG_MAXK], sgt[SEG_MAXK];
   for (int i = threadIdx.x; i < C * N; i += blockDim.x) sw[i] = W[i];
@@ -1431,7 +1435,7 @@ __global__ __launch_bounds__(256) void seg_dice_bwd_kernel(const float* __restri
     }
 #pragma unroll
     for (int c = 0; c < SEG_MAXC; ++c)
-      if (c < C) dbn[v * C + c] = out[c];
+      if (c < C) st1(dbn + v * C + c, out[c]);
   }
 }
 
@@ -1495,9 +1499,11 @@ __device__ __forceinline__ void shd_stage_head(float* wl, float* ssc, float* ssh
   for (int i = tid; i < 64; i += 256) sb[i] = i < N ? b[column(i)] : 0.f;
 }
 
-// xw [16][SX] <- op(x[v0 + r][c], c) of a wave's 16 voxels (rows past the volume: zeros)
-template <typename Op>
-__device__ __forceinline__ void shd_stage_rows(float* xw, int SX, const float* __restrict__ x, int64_t v0, int64_t nvox, int C,
+// xw [16][SX] <- op(x[v0 + r][c], c) of a wave's 16 voxels (rows past the volume: zeros).  T = float | bf16_t: a bf16 row is
+// half as wide in global memory (4 channels = one 8-byte load); its fp32 image in LDS keeps the stride SX, so what the comment
+// above SHD_TILE says about banks holds for both.
+template <typename T, typename Op>
+__device__ __forceinline__ void shd_stage_rows(float* xw, int SX, const T* __restrict__ x, int64_t v0, int64_t nvox, int C,
                                                Op op) {
   const int lane = threadIdx.x & 63, C4 = C >> 2;
 #pragma unroll
@@ -1625,6 +1631,43 @@ __global__ __launch_bounds__(256) void seg_head_dice_fwd_kernel(const float* __r
   if (syn_det_gather(st, 2 * N))
     for (int i = tid; i < 2 * N; i += 256) atomicAdd(&sums[i], st[i]);
   syn_det_gather_end(2 * N);
+}
+
+// probs[v][n] = softmax_n(bn(x[v]) . w + b) of a bf16 feature map: seg_head_dice_fwd_kernel without labels and sums (the head of
+// a frozen or inference bf16 network; BatchNorm, head and softmax in fp32 on the fp32 master weights).  LDS: ShdFwdLds(C, N, false).
+__global__ __launch_bounds__(256) void seg_head_fwd_bf16_kernel(const bf16_t* __restrict__ x, int64_t nvox, int C,
+                                                                const float* __restrict__ stats,
+                                                                const float* __restrict__ gamma,
+                                                                const float* __restrict__ beta, float eps,
+                                                                const float* __restrict__ W, const float* __restrict__ b, int N,
+                                                                float* __restrict__ probs) {
+  extern __shared__ float smem[];
+  const ShdFwdLds L(C, N, false);
+  const int NB = (N + 15) >> 4, SX = L.SX, SW = L.SW;
+  float *wl = smem, *ssc = smem + L.scale, *ssh = smem + L.shift, *sb = smem + L.bias;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, col = lane & 15, quad = lane >> 4;
+  shd_stage_head(wl, ssc, ssh, sb, SW, C, N, stats, gamma, beta, eps, W, b, [](int n) { return n; });
+  __syncthreads();
+  float* xw = smem + L.xs + wave * 16 * SX;
+  for (int64_t base = (int64_t)blockIdx.x * SHD_TILE; base < nvox; base += (int64_t)gridDim.x * SHD_TILE) {
+    const int64_t v0 = base + wave * 16;
+    shd_stage_rows(xw, SX, x, v0, nvox, C, [&](float a, int c) { return fmaf(a, ssc[c], ssh[c]); });  // BatchNorm output
+    __syncthreads();
+    shd_f32x4 acc[4];
+    shd_logits(acc, xw, wl, SX, SW, C, NB);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      float lg[4];
+      shd_row_logits(lg, acc, r, sb, NB, N);
+      const float inv = shd_row_softmax(lg, NB, N);
+      const int64_t v = v0 + 4 * quad + r;
+#pragma unroll
+      for (int nb = 0; nb < 4; ++nb) {
+        const int n = nb * 16 + col;
+        if (nb < NB && n < N && v < nvox) probs[v * N + n] = lg[nb] * inv;
+      }
+    }
+  }
 }
 
 // Backward of scale * mean_n(1 - (T_n + e) / (B_n + e)) through the softmax, the head and into the last BatchNorm's output:
@@ -1795,8 +1838,9 @@ __global__ __launch_bounds__(256) void seg_head_dice_bwd_kernel(const float* __r
 //                permuted order, so lane n holds the flipped pass's posterior of channel perm[n] and reads prev in place.
 //                Label and, if probs_out, p are written at mirror(v): the outputs are in the unflipped frame.  probs_out
 //                must not overlap prev.
-template <bool TTA>
-__device__ __forceinline__ void shd_label_sweep(const float* __restrict__ x, int64_t nvox, int C,
+// T = the element type of x (float | bf16_t); everything after the staging is the same fp32 code.
+template <bool TTA, typename T>
+__device__ __forceinline__ void shd_label_sweep(const T* __restrict__ x, int64_t nvox, int C,
                                                 const float* __restrict__ stats, const float* __restrict__ gamma,
                                                 const float* __restrict__ beta, float eps, const float* __restrict__ W,
                                                 const float* __restrict__ b, int N, const int32_t* __restrict__ labels,
@@ -1872,7 +1916,8 @@ __device__ __forceinline__ void shd_label_sweep(const float* __restrict__ x, int
   }
 }
 
-__global__ __launch_bounds__(256) void seg_head_argmax_kernel(const float* __restrict__ x, int64_t nvox, int C,
+template <typename T>
+__global__ __launch_bounds__(256) void seg_head_argmax_kernel(const T* __restrict__ x, int64_t nvox, int C,
                                                               const float* __restrict__ stats,
                                                               const float* __restrict__ gamma,
                                                               const float* __restrict__ beta, float eps,
@@ -1881,7 +1926,8 @@ __global__ __launch_bounds__(256) void seg_head_argmax_kernel(const float* __res
   shd_label_sweep<false>(x, nvox, C, stats, gamma, beta, eps, W, b, N, labels, nullptr, nullptr, 1, nvox, out, nullptr);
 }
 
-__global__ __launch_bounds__(256) void seg_head_tta_argmax_kernel(const float* __restrict__ x, int64_t nvox, int C,
+template <typename T>
+__global__ __launch_bounds__(256) void seg_head_tta_argmax_kernel(const T* __restrict__ x, int64_t nvox, int C,
                                                                   const float* __restrict__ stats,
                                                                   const float* __restrict__ gamma,
                                                                   const float* __restrict__ beta, float eps,
@@ -2183,6 +2229,63 @@ static int scale_channels_t(const T* x, T* out, int64_t nvox, int C, const float
   return SYNTHSR_OK;
 }
 
+// ---- the softmax-head entry points that exist for float and bf16_t
+template <typename T>
+static int seg_dice_bwd_t(const float* probs, const int32_t* seg, int64_t nvox, int C, int N, const float* w,
+                          const int32_t* cls_idx, const int32_t* cls_gt, int K, const float* sums, float scale, T* dbn,
+                          synthsr_stream_t stream) {
+  if (!probs || !seg || !w || !cls_idx || !cls_gt || !sums || !dbn || nvox < 1 || C < 1 || C > SEG_MAXC || N < 1 ||
+      N > SEG_MAXN || K < 1 || K > SEG_MAXK)
+    return SYNTHSR_EINVAL;
+  hipLaunchKernelGGL(seg_dice_bwd_kernel<T>, dim3(syn_grid(nvox, 256)), dim3(256), 0, (hipStream_t)stream, probs, seg, nvox, C,
+                     N, w, cls_idx, cls_gt, K, sums, scale, dbn);
+  SYN_CHECK_LAUNCH();
+  return SYNTHSR_OK;
+}
+
+// limits of the tile kernels below (checked before any launch): C <= 64 in whole channel quads, N <= 64, x aligned to the
+// vector load of one channel quad: 16 bytes for float, 8 bytes for bf16 (xalign)
+static bool shd_ok(int64_t nvox, int C, int N, int lut_n, const void* x, int xalign = 16) {
+  return nvox >= 1 && C >= 4 && C <= SEG_MAXC && (C % 4) == 0 && N >= 1 && N <= SEG_MAXN && lut_n >= 1 &&
+         ((uintptr_t)x % xalign) == 0;
+}
+
+// the two label-map kernels: the limits of the Dice head, at least two classes; T = float | bf16_t, the element type of x
+template <typename T>
+static bool shd_label_ok(int64_t nvox, int C, int N, const T* x) { return N >= 2 && shd_ok(nvox, C, N, 1, x, 4 * sizeof(T)); }
+
+template <typename T>
+static int seg_head_argmax_t(const T* x, int64_t nvox, int C, const float* stats, const float* gamma, const float* beta,
+                             float eps, const float* w, const float* b, int N, const int32_t* labels, int32_t* out,
+                             synthsr_stream_t stream) {
+  if (!x || !stats || !gamma || !beta || !w || !b || !labels || !out || !shd_label_ok(nvox, C, N, x)) return SYNTHSR_EINVAL;
+  hipLaunchKernelGGL(seg_head_argmax_kernel<T>, dim3(syn_grid(nvox, SHD_TILE, head_grid())), dim3(256),
+                     ShdFwdLds(C, N, false).total * sizeof(float), (hipStream_t)stream, x, nvox, C, stats, gamma, beta, eps, w, b, N,
+                     labels, out);
+  SYN_CHECK_LAUNCH();
+  return SYNTHSR_OK;
+}
+
+template <typename T>
+static int seg_head_tta_argmax_t(const T* x, const int* shape, int C, const float* stats, const float* gamma,
+                                 const float* beta, float eps, const float* w, const float* b, int N, const int32_t* labels,
+                                 const float* prev, const int32_t* perm, int32_t* out, float* probs_out,
+                                 synthsr_stream_t stream) {
+  if (!shape || shape[0] < 1 || shape[1] < 1 || shape[2] < 1) return SYNTHSR_EINVAL;
+  const int64_t plane = (int64_t)shape[1] * shape[2], nvox = plane * shape[0];
+  if (!x || !stats || !gamma || !beta || !w || !b || !labels || !prev || !perm || !out || !shd_label_ok(nvox, C, N, x))
+    return SYNTHSR_EINVAL;
+  if (probs_out) {  // written at the mirrored voxel while other workgroups still read prev: the two may not share memory
+    const uintptr_t p0 = (uintptr_t)prev, q0 = (uintptr_t)probs_out, bytes = (uintptr_t)nvox * N * sizeof(float);
+    if (p0 < q0 + bytes && q0 < p0 + bytes) return SYNTHSR_EINVAL;
+  }
+  hipLaunchKernelGGL(seg_head_tta_argmax_kernel<T>, dim3(syn_grid(nvox, SHD_TILE, head_grid())), dim3(256),
+                     ShdFwdLds(C, N, false).total * sizeof(float), (hipStream_t)stream, x, nvox, C, stats, gamma, beta, eps, w, b, N,
+                     labels, prev, perm, shape[0], plane, out, probs_out);
+  SYN_CHECK_LAUNCH();
+  return SYNTHSR_OK;
+}
+
 extern "C" {
 
 // ELU / ReLU backward (act 1 ELU, 3 ReLU; anything else SYNTHSR_EINVAL): four entry-point families on the one launcher.  The
@@ -2478,18 +2581,23 @@ int synthsr_seg_dice_sums(const float* probs, const int32_t* seg, int64_t nvox, 
 int synthsr_seg_dice_bwd(const float* probs, const int32_t* seg, int64_t nvox, int C, int N, const float* w,
                          const int32_t* cls_idx, const int32_t* cls_gt, int K, const float* sums, float scale, float* dbn,
                          synthsr_stream_t stream) {
-  if (!probs || !seg || !w || !cls_idx || !cls_gt || !sums || !dbn || nvox < 1 || C < 1 || C > SEG_MAXC || N < 1 ||
-      N > SEG_MAXN || K < 1 || K > SEG_MAXK)
-    return SYNTHSR_EINVAL;
-  hipLaunchKernelGGL(seg_dice_bwd_kernel, dim3(syn_grid(nvox, 256)), dim3(256), 0, (hipStream_t)stream, probs, seg, nvox, C,
-                     N, w, cls_idx, cls_gt, K, sums, scale, dbn);
-  SYN_CHECK_LAUNCH();
-  return SYNTHSR_OK;
+  return seg_dice_bwd_t<float>(probs, seg, nvox, C, N, w, cls_idx, cls_gt, K, sums, scale, dbn, stream);
+}
+int synthsr_seg_dice_bwd_bf16(const float* probs, const int32_t* seg, int64_t nvox, int C, int N, const float* w,
+                              const int32_t* cls_idx, const int32_t* cls_gt, int K, const float* sums, float scale, void* dbn,
+                              synthsr_stream_t stream) {
+  return seg_dice_bwd_t<bf16_t>(probs, seg, nvox, C, N, w, cls_idx, cls_gt, K, sums, scale, (bf16_t*)dbn, stream);
 }
 
-// limits of the two kernels below (checked before any launch): C <= 64 in whole channel quads, N <= 64, x 16-byte aligned
-static bool shd_ok(int64_t nvox, int C, int N, int lut_n, const void* x) {
-  return nvox >= 1 && C >= 4 && C <= SEG_MAXC && (C % 4) == 0 && N >= 1 && N <= SEG_MAXN && lut_n >= 1 && ((uintptr_t)x % 16) == 0;
+// posteriors of a bf16 feature map on the tile body (the fp32 synthsr_seg_head_fwd keeps its one-thread-per-voxel kernel)
+int synthsr_seg_head_fwd_bf16(const void* x, int64_t nvox, int C, const float* stats, const float* gamma, const float* beta,
+                              float eps, const float* w, const float* b, int N, float* probs, synthsr_stream_t stream) {
+  if (!x || !stats || !gamma || !beta || !w || !b || !probs || !shd_ok(nvox, C, N, 1, x, 8)) return SYNTHSR_EINVAL;
+  hipLaunchKernelGGL(seg_head_fwd_bf16_kernel, dim3(syn_grid(nvox, SHD_TILE, head_grid())), dim3(256),
+                     ShdFwdLds(C, N, false).total * sizeof(float), (hipStream_t)stream, (const bf16_t*)x, nvox, C, stats, gamma,
+                     beta, eps, w, b, N, probs);
+  SYN_CHECK_LAUNCH();
+  return SYNTHSR_OK;
 }
 
 int synthsr_seg_head_dice_fwd(const float* x, int64_t nvox, int C, const float* stats, const float* gamma, const float* beta,
@@ -2517,37 +2625,29 @@ int synthsr_seg_head_dice_bwd(const float* probs, const int32_t* seg, const int3
   return SYNTHSR_OK;
 }
 
-// the two label-map kernels: the limits of the Dice head, at least two classes
-static bool shd_label_ok(int64_t nvox, int C, int N, const void* x) { return N >= 2 && shd_ok(nvox, C, N, 1, x); }
-
 int synthsr_seg_head_argmax(const float* x, int64_t nvox, int C, const float* stats, const float* gamma, const float* beta,
                             float eps, const float* w, const float* b, int N, const int32_t* labels, int32_t* out,
                             synthsr_stream_t stream) {
-  if (!x || !stats || !gamma || !beta || !w || !b || !labels || !out || !shd_label_ok(nvox, C, N, x)) return SYNTHSR_EINVAL;
-  hipLaunchKernelGGL(seg_head_argmax_kernel, dim3(syn_grid(nvox, SHD_TILE, head_grid())), dim3(256),
-                     ShdFwdLds(C, N, false).total * sizeof(float), (hipStream_t)stream, x, nvox, C, stats, gamma, beta, eps, w, b, N,
-                     labels, out);
-  SYN_CHECK_LAUNCH();
-  return SYNTHSR_OK;
+  return seg_head_argmax_t<float>(x, nvox, C, stats, gamma, beta, eps, w, b, N, labels, out, stream);
+}
+int synthsr_seg_head_argmax_bf16(const void* x, int64_t nvox, int C, const float* stats, const float* gamma, const float* beta,
+                                 float eps, const float* w, const float* b, int N, const int32_t* labels, int32_t* out,
+                                 synthsr_stream_t stream) {
+  return seg_head_argmax_t<bf16_t>((const bf16_t*)x, nvox, C, stats, gamma, beta, eps, w, b, N, labels, out, stream);
 }
 
 int synthsr_seg_head_tta_argmax(const float* x, const int* shape, int C, const float* stats, const float* gamma,
                                 const float* beta, float eps, const float* w, const float* b, int N, const int32_t* labels,
                                 const float* prev, const int32_t* perm, int32_t* out, float* probs_out,
                                 synthsr_stream_t stream) {
-  if (!shape || shape[0] < 1 || shape[1] < 1 || shape[2] < 1) return SYNTHSR_EINVAL;
-  const int64_t plane = (int64_t)shape[1] * shape[2], nvox = plane * shape[0];
-  if (!x || !stats || !gamma || !beta || !w || !b || !labels || !prev || !perm || !out || !shd_label_ok(nvox, C, N, x))
-    return SYNTHSR_EINVAL;
-  if (probs_out) {  // written at the mirrored voxel while other workgroups still read prev: the two may not share memory
-    const uintptr_t p0 = (uintptr_t)prev, q0 = (uintptr_t)probs_out, bytes = (uintptr_t)nvox * N * sizeof(float);
-    if (p0 < q0 + bytes && q0 < p0 + bytes) return SYNTHSR_EINVAL;
-  }
-  hipLaunchKernelGGL(seg_head_tta_argmax_kernel, dim3(syn_grid(nvox, SHD_TILE, head_grid())), dim3(256),
-                     ShdFwdLds(C, N, false).total * sizeof(float), (hipStream_t)stream, x, nvox, C, stats, gamma, beta, eps, w, b, N,
-                     labels, prev, perm, shape[0], plane, out, probs_out);
-  SYN_CHECK_LAUNCH();
-  return SYNTHSR_OK;
+  return seg_head_tta_argmax_t<float>(x, shape, C, stats, gamma, beta, eps, w, b, N, labels, prev, perm, out, probs_out, stream);
+}
+int synthsr_seg_head_tta_argmax_bf16(const void* x, const int* shape, int C, const float* stats, const float* gamma,
+                                     const float* beta, float eps, const float* w, const float* b, int N, const int32_t* labels,
+                                     const float* prev, const int32_t* perm, int32_t* out, float* probs_out,
+                                     synthsr_stream_t stream) {
+  return seg_head_tta_argmax_t<bf16_t>((const bf16_t*)x, shape, C, stats, gamma, beta, eps, w, b, N, labels, prev, perm, out,
+                                       probs_out, stream);
 }
 
 int synthsr_seg_label_counts(const int32_t* a, const int32_t* b, int64_t nvox, const int32_t* lut, int lut_n, int N,

@@ -777,13 +777,28 @@ def bn_elu_bwd_head(dpred, whead, y, stats, gamma, sums, dbias=None, out=None, e
     return out
 
 
+def _seg_fp32_rest(what, x, **rest):
+    """the softmax-head kernels take their feature map (or write dbn) as float32 or bfloat16; everything else is float32"""
+    if x.dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError('%s takes float32 or bfloat16 activations (got %s)' % (what, x.dtype))
+    for name, t in rest.items():
+        if t is not None and t.dtype != torch.float32:
+            raise ValueError('%s: %s stays float32 whatever the activations are (got %s)' % (what, name, t.dtype))
+
+
 def seg_head_fwd(x, stats, gamma, beta, w, b, probs, eps=BN_EPS):
-    """probs [nvox, N] = softmax(bn(x) @ w + b): head of the frozen segmentation U-Net"""
+    """probs [nvox, N] (float32) = softmax(bn(x) @ w + b): head of the frozen segmentation U-Net; x float32 or bfloat16
+    (bf16: the tile kernel of the softmax heads, C <= 64 in whole quads; BatchNorm, head and softmax in fp32)"""
     lib = _L()
     C = int(x.shape[-1])
-    _lib.check(lib.synthsr_seg_head_fwd(_lib.ptr(x), x.numel() // C, C, _lib.ptr(stats), _lib.ptr(gamma), _lib.ptr(beta),
-                                        eps, _lib.ptr(w), _lib.ptr(b), int(probs.shape[-1]), _lib.ptr(probs),
-                                        _lib.stream()), 'seg_head_fwd')
+    _seg_fp32_rest('seg_head_fwd', x, stats=stats, gamma=gamma, beta=beta, w=w, b=b, probs=probs)
+    N = int(probs.shape[-1])
+    if probs.numel() != (x.numel() // C) * N or w.numel() != C * N or b.numel() != N:
+        raise ValueError('seg_head_fwd: head [%d, %d] with a bias of %d and posteriors of %d values do not fit %d voxels'
+                         % (C, N, b.numel(), probs.numel(), x.numel() // C))
+    _lib.check(_sym('synthsr_seg_head_fwd', x)(_lib.ptr(x), x.numel() // C, C, _lib.ptr(stats), _lib.ptr(gamma),
+                                               _lib.ptr(beta), eps, _lib.ptr(w), _lib.ptr(b), N, _lib.ptr(probs),
+                                               _lib.stream()), 'seg_head_fwd')
     return probs
 
 
@@ -798,12 +813,13 @@ def seg_dice_sums(probs, seg, cls_idx, cls_gt, sums):
 
 
 def seg_dice_bwd(probs, seg, w, cls_idx, cls_gt, sums, scale, dbn):
-    """dbn [nvox, C] = d(scale * dice_loss)/d(BatchNorm output in front of the segmentation head)"""
-    lib = _L()
-    _lib.check(lib.synthsr_seg_dice_bwd(_lib.ptr(probs), _lib.ptr(seg), int(probs.shape[0]), int(dbn.shape[-1]),
-                                        int(probs.shape[1]), _lib.ptr(w), _lib.ptr(cls_idx), _lib.ptr(cls_gt),
-                                        int(cls_gt.numel()), _lib.ptr(sums), float(scale), _lib.ptr(dbn), _lib.stream()),
-               'seg_dice_bwd')
+    """dbn [nvox, C] = d(scale * dice_loss)/d(BatchNorm output in front of the segmentation head); dbn float32, or bfloat16
+    for a bf16 segmentation network (computed in fp32, rounded to nearest even at the store)"""
+    _seg_fp32_rest('seg_dice_bwd', dbn, probs=probs, w=w, sums=sums)
+    _lib.check(_sym('synthsr_seg_dice_bwd', dbn)(_lib.ptr(probs), _lib.ptr(seg), int(probs.shape[0]), int(dbn.shape[-1]),
+                                                 int(probs.shape[1]), _lib.ptr(w), _lib.ptr(cls_idx), _lib.ptr(cls_gt),
+                                                 int(cls_gt.numel()), _lib.ptr(sums), float(scale), _lib.ptr(dbn),
+                                                 _lib.stream()), 'seg_dice_bwd')
     return dbn
 
 
@@ -853,7 +869,8 @@ def seg_head_dice_bwd(probs, seg, lut, x, stats, gamma, beta, w, sums, dbn, dw, 
 
 
 def _seg_head_label_args(what, x, w, b, labels, out):
-    """shared checks of seg_head_argmax / _tta_argmax: float32 activations and head, int32 label values and label map"""
+    """shared checks of seg_head_argmax / _tta_argmax: float32 or bfloat16 activations, a float32 head, int32 label values
+    and label map"""
     if x.dim() != 4:
         raise ValueError('x should be [d0, d1, d2, C]')
     C = int(x.shape[-1])
@@ -862,8 +879,7 @@ def _seg_head_label_args(what, x, w, b, labels, out):
     if w.numel() != C * N or N < 2 or b.numel() != N or labels.numel() != N or out.numel() != nvox:
         raise ValueError('%s: head [%d, %d] with a bias of %d, %d label values and a label map of %d values do not fit %d voxels'
                          % (what, C, N, b.numel(), labels.numel(), out.numel(), nvox))
-    if x.dtype != torch.float32 or w.dtype != torch.float32 or b.dtype != torch.float32:
-        raise ValueError('%s is fp32 only (x is %s)' % (what, x.dtype))
+    _seg_fp32_rest(what, x, w=w, b=b)
     if labels.dtype != torch.int32 or out.dtype != torch.int32:
         raise ValueError('%s takes the label values and writes the label map as int32 (got %s, %s)'
                          % (what, labels.dtype, out.dtype))
@@ -872,12 +888,13 @@ def _seg_head_label_args(what, x, w, b, labels, out):
 
 def seg_head_argmax(x, stats, gamma, beta, w, b, labels, out, eps=BN_EPS):
     """out [nvox] (int32) = labels[argmax_n(bn(x) @ w + b)]: the label map of a softmax head without its posteriors (the
-    argmax is taken on the logits; equal values: the lowest channel).  x [d0,d1,d2,C] with C <= 64, 2 <= N <= 64; labels
-    [N] int32: head channel -> label value"""
+    argmax is taken on the logits; equal values: the lowest channel).  x [d0,d1,d2,C] (float32 or bfloat16) with C <= 64,
+    2 <= N <= 64; labels [N] int32: head channel -> label value"""
     C, nvox, N = _seg_head_label_args('seg_head_argmax', x, w, b, labels, out)
-    _lib.check(_L().synthsr_seg_head_argmax(_lib.ptr(x), nvox, C, _lib.ptr(stats), _lib.ptr(gamma), _lib.ptr(beta), eps,
-                                            _lib.ptr(w), _lib.ptr(b), N, _lib.ptr(labels), _lib.ptr(out), _lib.stream()),
-               'seg_head_argmax')
+    _seg_fp32_rest('seg_head_argmax', x, stats=stats, gamma=gamma, beta=beta)
+    _lib.check(_sym('synthsr_seg_head_argmax', x)(_lib.ptr(x), nvox, C, _lib.ptr(stats), _lib.ptr(gamma), _lib.ptr(beta),
+                                                  eps, _lib.ptr(w), _lib.ptr(b), N, _lib.ptr(labels), _lib.ptr(out),
+                                                  _lib.stream()), 'seg_head_argmax')
     return out
 
 
@@ -891,10 +908,11 @@ def seg_head_tta_argmax(x, stats, gamma, beta, w, b, labels, prev, perm, out, pr
         raise ValueError('seg_head_tta_argmax: posteriors [%d, %d] and a permutation of %d channels are needed' % (nvox, N, N))
     if prev.dtype != torch.float32 or perm.dtype != torch.int32 or (probs_out is not None and probs_out.dtype != torch.float32):
         raise ValueError('seg_head_tta_argmax takes float32 posteriors and an int32 permutation')
-    _lib.check(_L().synthsr_seg_head_tta_argmax(_lib.ptr(x), _lib.i3(x.shape[:3]), C, _lib.ptr(stats), _lib.ptr(gamma),
-                                                _lib.ptr(beta), eps, _lib.ptr(w), _lib.ptr(b), N, _lib.ptr(labels),
-                                                _lib.ptr(prev), _lib.ptr(perm), _lib.ptr(out), _lib.ptr(probs_out),
-                                                _lib.stream()), 'seg_head_tta_argmax')
+    _seg_fp32_rest('seg_head_tta_argmax', x, stats=stats, gamma=gamma, beta=beta)
+    _lib.check(_sym('synthsr_seg_head_tta_argmax', x)(_lib.ptr(x), _lib.i3(x.shape[:3]), C, _lib.ptr(stats), _lib.ptr(gamma),
+                                                      _lib.ptr(beta), eps, _lib.ptr(w), _lib.ptr(b), N, _lib.ptr(labels),
+                                                      _lib.ptr(prev), _lib.ptr(perm), _lib.ptr(out), _lib.ptr(probs_out),
+                                                      _lib.stream()), 'seg_head_tta_argmax')
     return out
 
 

@@ -84,10 +84,14 @@ def check_head_width(state, table, labels):
 
 class SegmentationPredictor:
     """The softmax-headed U-Net of training_segmentation() (one input channel), rebuilt per padded volume shape like
-    predict.Predictor; one resident network."""
+    predict.Predictor; one resident network.  dtype 'bf16': bf16 activations and packed conv weights (the head, its
+    posteriors and the flip average stay fp32)."""
 
     def __init__(self, path_model, segmentation_label_list, n_levels=5, nb_conv_per_level=2, unet_feat_count=24,
-                 feat_multiplier=2, activation='elu', device=None, state_dict=None):
+                 feat_multiplier=2, activation='elu', device=None, state_dict=None, dtype='f32'):
+        if dtype not in ('f32', 'bf16'):
+            raise ValueError("dtype should be 'f32' or 'bf16', got %r" % (dtype,))
+        self.dtype = dtype
         self.labels = label_values(segmentation_label_list)
         self.lut = segmentation_lut(self.labels)
         self.arch = dict(nb_features=unet_feat_count, nb_levels=n_levels, conv_size=3, nb_labels=len(self.labels),
@@ -113,7 +117,8 @@ class SegmentationPredictor:
         key = tuple(int(s) for s in shape)
         if key not in self.nets:
             self.nets.clear()  # one resident network: volumes of a folder usually share their shape
-            net = unet(input_shape=list(key) + [1], conv_dropout=0, input_model=None, device=self.device, **self.arch)
+            net = unet(input_shape=list(key) + [1], conv_dropout=0, input_model=None, device=self.device, dtype=self.dtype,
+                       **self.arch)
             # a weight file with another layer prefix / missing layers must not leave random weights in place silently
             missing = [nm for nm, _, _ in net.specs if nm not in self.state]
             missing += [b['name'] + '/moving_mean' for b in net.bn_layers if b['name'] + '/moving_mean' not in self.state]
@@ -167,11 +172,14 @@ def _suffixed(path, suffix):
 
 def predict_segmentation(path_images, path_segmentations, path_model, segmentation_label_list, path_posteriors=None,
                          lr_pairs=None, disable_flipping=False, n_levels=5, nb_conv_per_level=2, unet_feat_count=24,
-                         feat_multiplier=2, activation='elu', device=None, verbose=True, predictor=None):
+                         feat_multiplier=2, activation='elu', device=None, verbose=True, predictor=None, dtype='f32'):
     """The file / folder contract of predict.predict(): `path_images` / `path_segmentations` (and `path_posteriors`, if
     given) are all single files (.nii, .nii.gz, .mgz, .npz) or all folders; in folders the outputs carry the suffixes
     `_seg` and `_posteriors`.  Label maps are saved as int32 in the 1 mm RAS frame predict() writes in.  Returns the paths
-    of the label maps."""
+    of the label maps.  dtype: 'f32' or 'bf16', the arithmetic of the network (SegmentationPredictor); posteriors are
+    written as float32 either way."""
+    if dtype not in ('f32', 'bf16'):
+        raise ValueError("dtype should be 'f32' or 'bf16', got %r" % (dtype,))
     if 32 % (2 ** (int(n_levels) - 1)) != 0:
         raise ValueError('volumes are padded to multiples of 32: n_levels = %d needs sides divisible by %d'
                          % (n_levels, 2 ** (int(n_levels) - 1)))
@@ -195,7 +203,7 @@ def predict_segmentation(path_images, path_segmentations, path_model, segmentati
         images, outs = [path_images], [path_segmentations]
         posts = [None if path_posteriors is None else os.path.abspath(path_posteriors)]
     predictor = predictor or SegmentationPredictor(path_model, segmentation_label_list, n_levels, nb_conv_per_level,
-                                                   unet_feat_count, feat_multiplier, activation, device)
+                                                   unet_feat_count, feat_multiplier, activation, device, dtype=dtype)
     if verbose:
         print('Found %d images' % len(images))
     for i, (pin, pout, ppost) in enumerate(zip(images, outs, posts)):

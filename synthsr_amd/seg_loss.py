@@ -108,6 +108,8 @@ class SegmentationRegulariser:
             seg = torch.where(mask, seg, torch.full_like(seg, -1))
             probs.mul_(mask[:, None])
         low, _ = net.saved['last']
+        # a bf16 seg_net: its buffers, hence dbn, are bf16 (seg_dice_bwd rounds at the store); posteriors and Dice sums stay
+        # fp32 and backward_input() hands the input gradient back as fp32, so everything below is the same for both
         dbn = net.buf('seg_dbn', list(low.shape))
         dice = None
         for b, (pb, sb, db) in enumerate(zip(probs.chunk(nb, 0), seg.chunk(nb, 0), dbn.chunk(nb, 0))):

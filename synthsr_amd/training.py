@@ -428,7 +428,7 @@ def training(labels_dir, model_dir, prior_means, prior_stds, path_generation_lab
              feat_multiplier=2, dropout=0, activation='elu', lr=1e-4, lr_decay=0, epochs=100, steps_per_epoch=1000,
              regression_metric='l1', work_with_residual_channel=None, loss_cropping=None, checkpoint=None,
              model_file_has_different_lhood_layer=False, seed=0, verbose=True, dtype='f32', deterministic=False,
-             segnet_frozen_bn='batch', reference_batch_gmm=False):
+             segnet_frozen_bn='batch', reference_batch_gmm=False, segnet_dtype=None):
     """Parameters as documented in SynthSR/training.py:90-240 (+ `reference_batch_gmm`: at batchsize > 1 sample every item
     from the SUM of the batch's GMM means / stds like the reference's SampleConditionalGMM does (a bug; off: each
     item from its own); `seed`, `verbose`, `dtype`: 'f32' like the reference, or
@@ -436,8 +436,12 @@ def training(labels_dir, model_dir, prior_means, prior_stds, path_generation_lab
     BASELINE.json configs[3]; `deterministic`: bit-identical weights run after run for the same seed, ops.set_deterministic,
     1.2x (fp32) / 1.4x (bf16) slower at 160^3; `segnet_frozen_bn`: what the frozen
     segmentation network's BatchNormalization normalises with, 'batch' = the statistics of its own activations, which is what
-    Keras 2.3.1 does to a trainable=False BatchNormalization under fit(), or 'inference' = its moving averages)."""
+    Keras 2.3.1 does to a trainable=False BatchNormalization under fit(), or 'inference' = its moving averages;
+    `segnet_dtype`: the arithmetic of that frozen network, None / 'f32' = fp32 whatever `dtype` is, 'bf16' = bf16 activations
+    and packed weights like `dtype`; its posteriors, Dice sums and the gradient handed back to the image loss stay fp32)."""
     import torch
+    if segnet_dtype not in (None, 'f32', 'bf16'):
+        raise ValueError("segnet_dtype should be None, 'f32' or 'bf16', got %r" % (segnet_dtype,))
     if deterministic:  # process-wide switch: on for the duration of this call, previous setting restored on the way out
         from . import ops as _ops
         kw = dict(locals())
@@ -556,7 +560,8 @@ def training(labels_dir, model_dir, prior_means, prior_stds, path_generation_lab
         seg_net = build_unet(nb_features=unet_feat_count, input_shape=seg_shape + [1], nb_levels=n_levels,
                              conv_size=conv_size, nb_labels=len(segmentation_labels), feat_mult=feat_multiplier,
                              nb_conv_per_level=nb_conv_per_level, conv_dropout=dropout, final_pred_activation='softmax',
-                             batch_norm=-1, activation=activation, input_model=None, seed=seed + 1)
+                             batch_norm=-1, activation=activation, input_model=None, seed=seed + 1,
+                             dtype='bf16' if segnet_dtype == 'bf16' else 'f32')
         load_checkpoint(segmentation_model_file, seg_net)
         m = M = None
         if images_dir is not None:  # clip the synthesised images at the 2nd / 98th percentiles of the first real scan

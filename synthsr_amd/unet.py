@@ -354,7 +354,7 @@ class UNet3D:
 
     # ------------------------------------------------------------------ buffers
     _F32_BUFS = ('loss', 'dpred', 'pred', 'loss_unused', 'zero_t', 'probs', 'dwc', 'head_ab', 'dice_sums', 'probs_avg',
-                 'label_map')
+                 'label_map', 'dx_input_f32')
 
     def buf(self, key, shape):
         """persistent scratch tensor: activations / activation gradients in the network's dtype, the head's outputs,
@@ -789,8 +789,6 @@ class UNet3D:
         averaged posteriors [nvox, nb_labels] are returned as well.  Buffers of the network: valid until its next call."""
         if self.final_pred_activation != 'softmax':
             raise ValueError('predict_labels() is for softmax heads; use predict() for a linear head')
-        if self.bf16:
-            raise NotImplementedError('the segmentation head kernels are fp32 only (dtype=%r)' % 'bf16')
         if self.batch != 1:
             raise NotImplementedError('predict_labels() takes one volume per call (batch = %d)' % self.batch)
         if want_probs and prev is None:
@@ -822,9 +820,15 @@ class UNet3D:
 
     def backward_input(self, dbn):
         """gradient w.r.t. the network input of a loss whose gradient w.r.t. the LAST BatchNorm output is `dbn`
-        [d0,d1,d2,C]; the network is frozen: inference-mode BatchNorm (moving statistics), no weight gradients"""
+        [d0,d1,d2,C]; the network is frozen: inference-mode BatchNorm (moving statistics), no weight gradients.  A bf16
+        network takes dbn in bf16 and returns the input gradient as float32 [d0,d1,d2,Cin], without the padding channels of
+        its first conv's data gradient"""
         assert self.need_input_grad and not self.training
-        return self.backward(g_last=dbn, frozen=True)   # BatchNorm as in the forward pass (predict_probs: batch_stats)
+        g = self.backward(g_last=dbn, frozen=True)   # BatchNorm as in the forward pass (predict_probs: batch_stats)
+        if self.bf16:
+            cin = self.enc[0]['convs'][0]['cin']
+            g = self.buf('dx_input_f32', list(g.shape[:3]) + [cin]).copy_(g[..., :cin])
+        return g
 
     # ------------------------------------------------------------------ backward
     def backward(self, on_grad_ready=None, g_last=None, frozen=False):
@@ -1093,17 +1097,25 @@ class UNet3D:
             g2 = None
             fused = False
             if j > 0 or need_dx:
-                out = self.buf('dx_%s_%d' % (tag, j & 1), list(xin.shape))
+                cin_e = c['cin']
+                if self.bf16 and cin_e % 4:
+                    # data gradient of a 1- or 2-channel first layer (backward_input): the kernel writes whole channel
+                    # quads and the packed weights carry zero rows for the padding (csrc/conv_bf16.hip:
+                    # synthsr_conv3d_bf16_pack_ex), so the launch and its output take the padded count
+                    cin_e = (cin_e + 3) // 4 * 4
+                    out = self.buf('dx_%s_%d' % (tag, j & 1), list(xin.shape[:3]) + [cin_e])
+                else:
+                    out = self.buf('dx_%s_%d' % (tag, j & 1), list(xin.shape))
                 # the ELU backward of the layer below (no BatchNorm in between) rides in the epilogue: one pass over
                 # the activation instead of three; its dbias comes out of the weight-gradient GEMM
                 below = acts[j - 1] if j > 0 else elu_below
                 if below is not None:
-                    self._pb(lambda dz_, b_, o_: ops.conv3d_add(dz_, c['wpd'], None, b_, c['cin'], self._act_dgrad, out=o_), dz, below, out)
+                    self._pb(lambda dz_, b_, o_: ops.conv3d_add(dz_, c['wpd'], None, b_, cin_e, self._act_dgrad, out=o_), dz, below, out)
                     if ps:  # the conv read s_b * ELU(below): the factor of the layer below's dropout on its gradient
                         ops.scale_channels(out, self._drop_ps[(convs[j - 1] if j > 0 else below_conv)['name']], out=out)
                     fused = True
                 else:
-                    self._pb(lambda dz_, o_: ops.conv3d(dz_, c['wpd'], None, c['cin'], 0, out=o_), dz, out)
+                    self._pb(lambda dz_, o_: ops.conv3d(dz_, c['wpd'], None, cin_e, 0, out=o_), dz, out)
                 g = out
             else:
                 g = None
