@@ -628,6 +628,29 @@ int synthsr_seg_head_dice_bwd(const float* probs, const int32_t* seg, const int3
                               const float* w, const float* sums, float scale, float* dbn, float* dw, float* db,
                               synthsr_stream_t stream);
 
+/* --- the weighted soft Dice: DiceLoss's class and boundary weights (ext/lab2im/layers.py:1347-1374) ----------------------
+ * boundary_mask: seg [shape[0]][shape[1]][shape[2]] and lut as above; mask [nvox] (uint64, 8-byte aligned) written: bit n of
+ *      mask[v] = [0 < 3 k < W], k = the voxels of class n and W = the voxels inside the volume among the (2 boundary_dist + 1)^3
+ *      window around v -- DiceLoss's [avg > 0][avg < 1/3 - 1e-4] on AvgPool3D('same') of the one-hot, exactly, in integers.
+ *      Voxels without a class count in W only.  skip_background != 0 and N > 1: bit 0 stays clear.  1 <= boundary_dist <= 5
+ *      and N <= 64: anything else returns SYNTHSR_EINVAL before any launch.
+ * fwd_weighted / bwd_weighted: the two functions above with w_n(v) = 1 + boundary_weights * bit n of mask[v] on every term
+ *      (mask NULL: w = 1) and the loss sum_n c_n (1 - dice_n), c = class_weights [N] (device; constants of the step):
+ *      sums [3 N] (zeroed by the caller): sums[n] += w 2 gt p, sums[N + n] += w (gt^2 + p^2), sums[2 N + n] += w gt (the
+ *      weighted volume of class n, for "dynamic" class weights c_n ~ 1 / sums[2 N + n]);
+ *      bwd reads sums[0 .. 2 N): g_n = -scale c_n w_n (2 gt_n B_n - 2 p_n T_n) / B_n^2.  Limits of C and N as above. */
+int synthsr_seg_boundary_mask(const int32_t* seg, const int* shape, const int32_t* lut, int lut_n, int N, int boundary_dist,
+                              int skip_background, uint64_t* mask, synthsr_stream_t stream);
+int synthsr_seg_head_dice_fwd_weighted(const float* x, int64_t nvox, int C, const float* stats, const float* gamma,
+                                       const float* beta, float eps, const float* w, const float* b, int N, const int32_t* seg,
+                                       const int32_t* lut, int lut_n, const uint64_t* mask, float boundary_weights, float* probs,
+                                       float* sums, synthsr_stream_t stream);
+int synthsr_seg_head_dice_bwd_weighted(const float* probs, const int32_t* seg, const int32_t* lut, int lut_n, const float* x,
+                                       int64_t nvox, int C, int N, const float* stats, const float* gamma, const float* beta,
+                                       float eps, const float* w, const float* sums, const uint64_t* mask, float boundary_weights,
+                                       const float* class_weights, float scale, float* dbn, float* dw, float* db,
+                                       synthsr_stream_t stream);
+
 /* --- segmenting with a trained softmax-headed U-Net, scoring label maps (fp32) ------------------------------------------
  * x, stats / gamma / beta / eps (inference: the moving statistics), w, b as above; labels [N]: head channel -> label VALUE.
  * C <= 64 with C % 4 == 0, 2 <= N <= 64 (label_counts: 1 <= N <= 64): anything else returns SYNTHSR_EINVAL before any launch.

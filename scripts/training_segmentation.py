@@ -30,6 +30,11 @@ def build_parser():
     for flag, keyword, stored in SWITCHES:
         parser.add_argument('--' + flag, dest=keyword, action='store_true' if stored else 'store_false')
     parser.add_argument('--deterministic', dest='deterministic', action='store_true')
+    # the weights of the soft Dice (DiceLoss): class weights -1 = dynamic, or the path of a .npy with one value per label
+    parser.add_argument('--dice_class_weights', dest='dice_class_weights', type=str, default=None)
+    parser.add_argument('--dice_boundary_weights', dest='dice_boundary_weights', type=float, default=0.)
+    parser.add_argument('--dice_boundary_dist', dest='dice_boundary_dist', type=int, default=3)
+    parser.add_argument('--dice_no_skip_background', dest='dice_skip_background', action='store_false')
     return parser
 
 

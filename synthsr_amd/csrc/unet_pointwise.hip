@@ -1453,21 +1453,25 @@ __host__ __device__ constexpr int shd_stride(int blocks16) { return blocks16 * 1
 
 // The dynamic LDS of these kernels, offsets and total in floats: a kernel takes its pointers from here and its launcher the byte
 // count.  Forward and label-map kernels (wl at 0, <= 38 KB):
-//   wl [C][SW] | xs [4][16][SX] | scale, shift [64 + 64] | bias [64] | class or label value [64]; dice: | red [4][128] | st [128]
+//   wl [C][SW] | xs [4][16][SX] | scale, shift [64 + 64] | bias [64] | class or label value [64]; dice: | red [4][RS] | st [RS]
+// RS = 128 (rows T | B of 64); the weighted Dice: RS = 192 (T | B | V), then | boundary-mask words [64] (uint64: 128 floats)
 struct ShdFwdLds {
-  int SX, SW, xs, scale, shift, bias, cls, red, st, total;
-  __host__ __device__ constexpr ShdFwdLds(int C, int N, bool dice)
+  int SX, SW, xs, scale, shift, bias, cls, RS, red, st, msk, total;
+  __host__ __device__ constexpr ShdFwdLds(int C, int N, bool dice, bool weighted = false)
       : SX(shd_stride((C + 15) >> 4)), SW(shd_stride((N + 15) >> 4)), xs(C * SW), scale(xs + SHD_TILE * SX), shift(scale + 64),
-        bias(shift + 64), cls(bias + 64), red(cls + 64), st(red + 4 * 128), total(dice ? st + 128 : red) {}
+        bias(shift + 64), cls(bias + 64), RS(weighted ? 192 : 128), red(cls + 64), st(red + 4 * RS), msk(st + RS),
+        total(dice ? (weighted ? msk + 128 : msk) : red) {}
 };
 // Backward kernel (wl at 0; at most 3 x 64 x 68 + 320 floats = 53.5 KB, with the deterministic gather's 8 KB of static LDS inside
 // the 64 KB of a launch):
 //   wl [16 NB][SW] (w transposed, zero padded) | dl [4][16][SN] | xs [4][16][SX] | ga, gb [64 + 64] | mean, rstd [64 + 64] | class [64]
+// the weighted Dice: | boundary-mask words [64] (uint64: 128 floats; 54 KB + 8 KB at most)
 struct ShdBwdLds {
-  int NB, SX, SN, SW, dl, xs, ga, gb, mean, rstd, cls, total;
-  __host__ __device__ constexpr ShdBwdLds(int C, int N)
+  int NB, SX, SN, SW, dl, xs, ga, gb, mean, rstd, cls, msk, total;
+  __host__ __device__ constexpr ShdBwdLds(int C, int N, bool weighted = false)
       : NB((N + 15) >> 4), SX(shd_stride((C + 15) >> 4)), SN(shd_stride(NB)), SW(SX), dl(NB * 16 * SW), xs(dl + SHD_TILE * SN),
-        ga(xs + SHD_TILE * SX), gb(ga + 64), mean(gb + 64), rstd(mean + 64), cls(rstd + 64), total(cls + 64) {}
+        ga(xs + SHD_TILE * SX), gb(ga + 64), mean(gb + 64), rstd(mean + 64), cls(rstd + 64), msk(cls + 64),
+        total(weighted ? msk + 128 : msk) {}
 };
 // the byte counts of the three launchers these structs replaced, at the corners of C in {4 .. 64} x N in {1 .. 64}
 static_assert(ShdFwdLds(4, 1, true).total == 4 * 20 + 64 * 20 + 4 * 64 + 4 * 128 + 128 &&
@@ -1476,6 +1480,12 @@ static_assert(ShdFwdLds(4, 1, true).total == 4 * 20 + 64 * 20 + 4 * 64 + 4 * 128
               ShdBwdLds(4, 64).total == 64 * 20 + 64 * (68 + 20) + 5 * 64 && ShdBwdLds(64, 1).total == 16 * 68 + 64 * (20 + 68) + 5 * 64 &&
               ShdBwdLds(64, 64).total == 3 * 64 * 68 + 5 * 64,
               "LDS layout of the softmax-head kernels");
+// the weighted forms: the same offsets, wider sum rows and the mask words (8-byte aligned) behind everything else
+static_assert(ShdFwdLds(24, 33, true, true).cls == ShdFwdLds(24, 33, true).cls &&
+              ShdFwdLds(64, 64, true, true).total == ShdFwdLds(64, 64, true).total + 5 * 64 + 128 &&
+              ShdBwdLds(64, 64, true).total == ShdBwdLds(64, 64).total + 128 && ShdFwdLds(4, 1, true, true).msk % 2 == 0 &&
+              ShdBwdLds(4, 1, true).msk % 2 == 0 && (ShdBwdLds(64, 64, true).total * 4 + 8192 + 16) <= 65536,
+              "LDS layout of the weighted softmax-head kernels");
 
 // head channel of a label value, or -1
 __device__ __forceinline__ int shd_class(int lab, const int32_t* __restrict__ lut, int lut_n, int N) {
@@ -1565,6 +1575,11 @@ __device__ __forceinline__ float shd_row_softmax(float (&val)[4], int NB, int N)
 }
 
 // probs[v][n] = softmax_n(bn(x[v]) . w + b), sums[n] += 2 gt p, sums[N + n] += gt^2 + p^2: one pass, every voxel read once.
+// WEIGHTED (DiceLoss with boundary and / or class weights, ext/lab2im/layers.py:1347-1374): every term of voxel v and class n
+// counts w_n(v) = 1 + bw * bit n of mask[v] times (mask: seg_boundary_mask_kernel; nullptr = no boundary voxels), and a third
+// row sums[2 N + n] += w gt (the weighted volume of class n: dynamic class weights) is formed.  The mask word of a voxel is
+// staged next to its class index.  WEIGHTED = false never touches mask / bw: the kernel as it was.
+template <bool WEIGHTED>
 __global__ __launch_bounds__(256) void seg_head_dice_fwd_kernel(const float* __restrict__ x, int64_t nvox, int C,
                                                                 const float* __restrict__ stats,
                                                                 const float* __restrict__ gamma,
@@ -1572,9 +1587,11 @@ __global__ __launch_bounds__(256) void seg_head_dice_fwd_kernel(const float* __r
                                                                 const float* __restrict__ W, const float* __restrict__ b, int N,
                                                                 const int32_t* __restrict__ seg,
                                                                 const int32_t* __restrict__ lut, int lut_n,
-                                                                float* __restrict__ probs, float* __restrict__ sums) {
+                                                                float* __restrict__ probs, float* __restrict__ sums,
+                                                                const uint64_t* __restrict__ mask, float bw) {
   extern __shared__ float smem[];
-  const ShdFwdLds L(C, N, true);
+  const ShdFwdLds L(C, N, true, WEIGHTED);
+  constexpr int ROWS = WEIGHTED ? 3 : 2, RS = 64 * ROWS;
   const int NB = (N + 15) >> 4, SX = L.SX, SW = L.SW;
   float *wl = smem, *ssc = smem + L.scale, *ssh = smem + L.shift, *sb = smem + L.bias, *red = smem + L.red, *st = smem + L.st;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, col = lane & 15, quad = lane >> 4;
@@ -1582,11 +1599,15 @@ __global__ __launch_bounds__(256) void seg_head_dice_fwd_kernel(const float* __r
   __syncthreads();
   float* xw = smem + L.xs + wave * 16 * SX;
   int* cw = reinterpret_cast<int*>(smem + L.cls) + wave * 16;
-  float top[4] = {0.f, 0.f, 0.f, 0.f}, bot[4] = {0.f, 0.f, 0.f, 0.f};
+  uint64_t* mw = reinterpret_cast<uint64_t*>(smem + L.msk) + wave * 16;  // (WEIGHTED only)
+  float top[4] = {0.f, 0.f, 0.f, 0.f}, bot[4] = {0.f, 0.f, 0.f, 0.f}, vol[4] = {0.f, 0.f, 0.f, 0.f};
   for (int64_t base = (int64_t)blockIdx.x * SHD_TILE; base < nvox; base += (int64_t)gridDim.x * SHD_TILE) {
     const int64_t v0 = base + wave * 16;
     shd_stage_rows(xw, SX, x, v0, nvox, C, [&](float a, int c) { return fmaf(a, ssc[c], ssh[c]); });  // BatchNorm output
-    if (lane < 16) cw[lane] = v0 + lane < nvox ? shd_class(seg[v0 + lane], lut, lut_n, N) : -1;
+    if (lane < 16) {
+      cw[lane] = v0 + lane < nvox ? shd_class(seg[v0 + lane], lut, lut_n, N) : -1;
+      if constexpr (WEIGHTED) mw[lane] = (mask && v0 + lane < nvox) ? mask[v0 + lane] : 0ull;
+    }
     __syncthreads();
     shd_f32x4 acc[4];
     shd_logits(acc, xw, wl, SX, SW, C, NB);
@@ -1597,6 +1618,8 @@ __global__ __launch_bounds__(256) void seg_head_dice_fwd_kernel(const float* __r
       const float inv = shd_row_softmax(lg, NB, N);
       const int64_t v = v0 + 4 * quad + r;
       const int k = cw[4 * quad + r];
+      uint64_t m = 0;
+      if constexpr (WEIGHTED) m = mw[4 * quad + r];
 #pragma unroll
       for (int nb = 0; nb < 4; ++nb) {
         const int n = nb * 16 + col;
@@ -1604,8 +1627,15 @@ __global__ __launch_bounds__(256) void seg_head_dice_fwd_kernel(const float* __r
           const float p = lg[nb] * inv;
           probs[v * N + n] = p;
           const float gt = k == n ? 1.f : 0.f;
-          top[nb] += 2.f * gt * p;
-          bot[nb] += gt + p * p;
+          if constexpr (WEIGHTED) {
+            const float wgt = ((m >> n) & 1ull) ? 1.f + bw : 1.f, t = 2.f * gt * p, q = gt + p * p;
+            top[nb] += wgt * t;
+            bot[nb] += wgt * q;
+            vol[nb] += wgt * gt;
+          } else {
+            top[nb] += 2.f * gt * p;
+            bot[nb] += gt + p * p;
+          }
         }
       }
     }
@@ -1617,20 +1647,25 @@ __global__ __launch_bounds__(256) void seg_head_dice_fwd_kernel(const float* __r
     top[nb] += __shfl_xor(top[nb], 32, 64);
     bot[nb] += __shfl_xor(bot[nb], 16, 64);
     bot[nb] += __shfl_xor(bot[nb], 32, 64);
+    if constexpr (WEIGHTED) {
+      vol[nb] += __shfl_xor(vol[nb], 16, 64);
+      vol[nb] += __shfl_xor(vol[nb], 32, 64);
+    }
     if (lane < 16) {
-      red[wave * 128 + nb * 16 + lane] = top[nb];
-      red[wave * 128 + 64 + nb * 16 + lane] = bot[nb];
+      red[wave * RS + nb * 16 + lane] = top[nb];
+      red[wave * RS + 64 + nb * 16 + lane] = bot[nb];
+      if constexpr (WEIGHTED) red[wave * RS + 128 + nb * 16 + lane] = vol[nb];
     }
   }
   __syncthreads();
-  for (int i = tid; i < 2 * N; i += 256) {
-    const int k = i < N ? i : 64 + i - N;
-    st[i] = (red[k] + red[128 + k]) + (red[256 + k] + red[384 + k]);
+  for (int i = tid; i < ROWS * N; i += 256) {
+    const int row = i / N, k = 64 * row + i - row * N;
+    st[i] = (red[k] + red[RS + k]) + (red[2 * RS + k] + red[3 * RS + k]);
   }
   __syncthreads();
-  if (syn_det_gather(st, 2 * N))
-    for (int i = tid; i < 2 * N; i += 256) atomicAdd(&sums[i], st[i]);
-  syn_det_gather_end(2 * N);
+  if (syn_det_gather(st, ROWS * N))
+    for (int i = tid; i < ROWS * N; i += 256) atomicAdd(&sums[i], st[i]);
+  syn_det_gather_end(ROWS * N);
 }
 
 // probs[v][n] = softmax_n(bn(x[v]) . w + b) of a bf16 feature map: seg_head_dice_fwd_kernel without labels and sums (the head of
@@ -1677,6 +1712,10 @@ __global__ __launch_bounds__(256) void seg_head_fwd_bf16_kernel(const bf16_t* __
 // A wave keeps dlogit [16][SN] and xhat [16][SX] of its 16 voxels in LDS and forms dbn (K = classes) and A (K = voxels, the
 // accumulators live in registers for the whole sweep) on the matrix instruction.  The workgroup's partial A [N][C] | Bs [N] is
 // gathered in dl | xs after the sweep.
+// WEIGHTED: the loss is scale * sum_n c_n (1 - dice_n) on the weighted sums of seg_head_dice_fwd_kernel<true>:
+//   g_n = -scale c_n w_n(v) (2 gt_n (B_n + e) - 2 p_n (T_n + e)) / (B_n + e)^2,  w_n(v) = 1 + bw * bit n of mask[v]
+// (cwt [N]: the class weights c, constants of the step; mask nullptr = no boundary voxels); everything behind g is unchanged.
+template <bool WEIGHTED>
 __global__ __launch_bounds__(256) void seg_head_dice_bwd_kernel(const float* __restrict__ probs, const int32_t* __restrict__ seg,
                                                                 const int32_t* __restrict__ lut, int lut_n,
                                                                 const float* __restrict__ x, int64_t nvox, int C, int N,
@@ -1685,9 +1724,10 @@ __global__ __launch_bounds__(256) void seg_head_dice_bwd_kernel(const float* __r
                                                                 const float* __restrict__ beta, float eps,
                                                                 const float* __restrict__ W, const float* __restrict__ sums,
                                                                 float scale, float* __restrict__ dbn, float* __restrict__ dw,
-                                                                float* __restrict__ db) {
+                                                                float* __restrict__ db, const uint64_t* __restrict__ mask,
+                                                                float bw, const float* __restrict__ cwt) {
   extern __shared__ float smem[];
-  const ShdBwdLds L(C, N);
+  const ShdBwdLds L(C, N, WEIGHTED);
   const int NB = L.NB, CB = (C + 15) >> 4, SX = L.SX, SN = L.SN, SW = L.SW;
   float *wl = smem, *dl = smem + L.dl, *xs = smem + L.xs, *sga = smem + L.ga, *sgb = smem + L.gb, *smean = smem + L.mean,
         *srstd = smem + L.rstd;
@@ -1698,10 +1738,12 @@ __global__ __launch_bounds__(256) void seg_head_dice_bwd_kernel(const float* __r
     wl[i] = (n < N && c < C) ? W[c * N + n] : 0.f;
   }
   for (int i = tid; i < SHD_TILE * (SN + SX); i += 256) dl[i] = 0.f;  // the padding columns stay zero
-  const float coef = -scale / (float)N;
+  const float coef_mean = -scale / (float)N;
   for (int i = tid; i < 64; i += 256) {
     float ga = 0.f, gb = 0.f;
     if (i < N) {
+      float coef = coef_mean;
+      if constexpr (WEIGHTED) coef = -scale * cwt[i];
       const float T = sums[i] + 1e-7f, B = sums[N + i] + 1e-7f;
       ga = coef * 2.f / B;
       gb = coef * 2.f * T / (B * B);
@@ -1717,6 +1759,7 @@ __global__ __launch_bounds__(256) void seg_head_dice_bwd_kernel(const float* __r
   float* dlw = dl + wave * 16 * SN;
   float* xw = xs + wave * 16 * SX;
   int* cw = scls + wave * 16;
+  uint64_t* mw = reinterpret_cast<uint64_t*>(smem + L.msk) + wave * 16;  // (WEIGHTED only)
   shd_f32x4 accA[4][4];
 #pragma unroll
   for (int nb = 0; nb < 4; ++nb)
@@ -1739,21 +1782,29 @@ __global__ __launch_bounds__(256) void seg_head_dice_bwd_kernel(const float* __r
         }
       }
     }
-    if (lane < 16) cw[lane] = v0 + lane < nvox ? shd_class(seg[v0 + lane], lut, lut_n, N) : -1;
+    if (lane < 16) {
+      cw[lane] = v0 + lane < nvox ? shd_class(seg[v0 + lane], lut, lut_n, N) : -1;
+      if constexpr (WEIGHTED) mw[lane] = (mask && v0 + lane < nvox) ? mask[v0 + lane] : 0ull;
+    }
     __syncthreads();
     {  // four lanes per voxel: S = sum_n g_n p_n, then dlogit in place
       const int r = lane >> 2, q = lane & 3, k = cw[r];
+      uint64_t m = 0;
+      if constexpr (WEIGHTED) m = mw[r];
+      const float wb = 1.f + bw;
       float S = 0.f;
       for (int n = q; n < N; n += 4) {
         const float p = dlw[r * SN + n];
-        const float g = (k == n ? sga[n] : 0.f) - p * sgb[n];
+        float g = (k == n ? sga[n] : 0.f) - p * sgb[n];
+        if constexpr (WEIGHTED) g *= ((m >> n) & 1ull) ? wb : 1.f;
         S = fmaf(g, p, S);
       }
       S += __shfl_xor(S, 1, 64);
       S += __shfl_xor(S, 2, 64);
       for (int n = q; n < N; n += 4) {
         const float p = dlw[r * SN + n];
-        const float g = (k == n ? sga[n] : 0.f) - p * sgb[n];
+        float g = (k == n ? sga[n] : 0.f) - p * sgb[n];
+        if constexpr (WEIGHTED) g *= ((m >> n) & 1ull) ? wb : 1.f;
         dlw[r * SN + n] = p * (g - S);
       }
     }
@@ -1824,6 +1875,83 @@ __global__ __launch_bounds__(256) void seg_head_dice_bwd_kernel(const float* __r
     if (tid < N) atomicAdd(&db[tid], part[N * C + tid]);
   }
   syn_det_gather_end(N * C + N);
+}
+
+// ------------------------------------------------------------------ boundary voxels of a label map (weighted soft Dice)
+// DiceLoss's boundary map (ext/lab2im/layers.py:1349-1353) without its one-hot tensors: bit n of mask[v] says whether voxel v
+// counts 1 + boundary_weights times for class n,
+//   bnd_n(v) = [avg_n(v) > 0] [avg_n(v) < 1/3 - 1e-4],  avg_n = AvgPool3D(2 d + 1, strides 1, 'same') of the one-hot of lut[seg]
+// (padding is not part of the divisor).  In integers: with k the voxels of class n and Wn the voxels inside the volume in the
+// (2 d + 1)^3 window, bnd_n(v) = [0 < 3 k < Wn] -- the float rule exactly while Wn < 3333 (k / Wn < 1/3 is at most
+// 1/3 - 1 / (3 Wn)), i.e. for d <= 5.  Voxels without a class count in Wn and in no k.  No floating point anywhere.
+// A workgroup stages the class indices (one byte each, 255 = no class) of a 4 x 8 x 32 tile and its halo of d in LDS; a thread
+// owns one (y, x) column of the tile.  Per voxel: one sweep of the window ORs the classes present and counts the classed voxels,
+// then one counting sweep per class present but the last, whose count is what is left (an interior voxel: no second sweep).
+// Taps outside the volume are neither read nor counted.
+constexpr int SBM_TZ = 4, SBM_TY = 8, SBM_TX = 32, SBM_MAXD = 5;
+constexpr int SBM_LDS = (SBM_TZ + 2 * SBM_MAXD) * (SBM_TY + 2 * SBM_MAXD) * (SBM_TX + 2 * SBM_MAXD);
+__global__ __launch_bounds__(256) void seg_boundary_mask_kernel(const int32_t* __restrict__ seg, int d0, int d1, int d2,
+                                                                const int32_t* __restrict__ lut, int lut_n, int N, int d,
+                                                                int skip_bg, uint64_t* __restrict__ mask) {
+  __shared__ uint8_t tile[SBM_LDS];
+  const int HY = SBM_TY + 2 * d, HX = SBM_TX + 2 * d, HN = (SBM_TZ + 2 * d) * HY * HX;
+  const int t0 = (d0 + SBM_TZ - 1) / SBM_TZ, t1 = (d1 + SBM_TY - 1) / SBM_TY, t2 = (d2 + SBM_TX - 1) / SBM_TX;
+  const int tid = threadIdx.x, tx = tid & (SBM_TX - 1), ty = tid / SBM_TX;
+  for (int t = blockIdx.x; t < t0 * t1 * t2; t += gridDim.x) {
+    const int tz_ = t / (t1 * t2), tr = t - tz_ * (t1 * t2), ty_ = tr / t2;
+    const int z0 = tz_ * SBM_TZ - d, y0 = ty_ * SBM_TY - d, x0 = (tr - ty_ * t2) * SBM_TX - d;  // origin of the staged block
+    for (int i = tid; i < HN; i += 256) {
+      const int hz = i / (HY * HX), hr = i - hz * (HY * HX), hy = hr / HX, hx = hr - hy * HX;
+      const int z = z0 + hz, y = y0 + hy, xx = x0 + hx;
+      int k = -1;
+      if (z >= 0 && z < d0 && y >= 0 && y < d1 && xx >= 0 && xx < d2)
+        k = shd_class(seg[((int64_t)z * d1 + y) * d2 + xx], lut, lut_n, N);
+      tile[i] = (uint8_t)(k < 0 ? 255 : k);
+    }
+    __syncthreads();
+    const int Y = y0 + d + ty, X = x0 + d + tx;
+    if (Y < d1 && X < d2) {
+      const int ya = max(Y - d, 0) - y0, yb = min(Y + d, d1 - 1) - y0, xa = max(X - d, 0) - x0, xb = min(X + d, d2 - 1) - x0;
+      for (int tz = 0; tz < SBM_TZ; ++tz) {
+        const int Z = z0 + d + tz;
+        if (Z >= d0) break;
+        const int za = max(Z - d, 0) - z0, zb = min(Z + d, d0 - 1) - z0;
+        const int Wn = (zb - za + 1) * (yb - ya + 1) * (xb - xa + 1);
+        uint64_t present = 0;
+        int left = 0;
+        for (int z = za; z <= zb; ++z)
+          for (int y = ya; y <= yb; ++y) {
+            const uint8_t* row = tile + (z * HY + y) * HX;
+            for (int xx = xa; xx <= xb; ++xx) {
+              const int c = row[xx];
+              if (c < 64) {
+                present |= 1ull << c;
+                ++left;
+              }
+            }
+          }
+        uint64_t bits = 0;
+        while (present) {
+          const int n = __builtin_ctzll(present);
+          present &= present - 1;
+          int k = left;  // the last class present: what the others left
+          if (present) {
+            k = 0;
+            for (int z = za; z <= zb; ++z)
+              for (int y = ya; y <= yb; ++y) {
+                const uint8_t* row = tile + (z * HY + y) * HX;
+                for (int xx = xa; xx <= xb; ++xx) k += row[xx] == n ? 1 : 0;
+              }
+            left -= k;
+          }
+          if (3 * k < Wn) bits |= 1ull << n;
+        }
+        if (skip_bg) bits &= ~1ull;
+        mask[((int64_t)Z * d1 + Y) * d2 + X] = bits;
+      }
+    }
+    __syncthreads();
+  }
 }
 
 // ------------------------------------------------------------------ softmax head -> label map (inference, fp32)
@@ -2605,9 +2733,37 @@ int synthsr_seg_head_dice_fwd(const float* x, int64_t nvox, int C, const float* 
                               int lut_n, float* probs, float* sums, synthsr_stream_t stream) {
   if (!x || !stats || !gamma || !beta || !w || !b || !seg || !lut || !probs || !sums || !shd_ok(nvox, C, N, lut_n, x))
     return SYNTHSR_EINVAL;
-  hipLaunchKernelGGL(seg_head_dice_fwd_kernel, dim3(syn_grid(nvox, SHD_TILE, head_grid())), dim3(256),
+  hipLaunchKernelGGL(seg_head_dice_fwd_kernel<false>, dim3(syn_grid(nvox, SHD_TILE, head_grid())), dim3(256),
                      ShdFwdLds(C, N, true).total * sizeof(float), (hipStream_t)stream, x, nvox, C, stats, gamma, beta, eps, w, b, N,
-                     seg, lut, lut_n, probs, sums);
+                     seg, lut, lut_n, probs, sums, (const uint64_t*)nullptr, 0.f);
+  SYN_CHECK_LAUNCH();
+  return SYNTHSR_OK;
+}
+
+// the weighted soft Dice: sums [3 N]; mask may be NULL (class weights without boundary weighting)
+int synthsr_seg_head_dice_fwd_weighted(const float* x, int64_t nvox, int C, const float* stats, const float* gamma,
+                                       const float* beta, float eps, const float* w, const float* b, int N, const int32_t* seg,
+                                       const int32_t* lut, int lut_n, const uint64_t* mask, float boundary_weights, float* probs,
+                                       float* sums, synthsr_stream_t stream) {
+  if (!x || !stats || !gamma || !beta || !w || !b || !seg || !lut || !probs || !sums || !shd_ok(nvox, C, N, lut_n, x) ||
+      ((uintptr_t)mask % 8) != 0)
+    return SYNTHSR_EINVAL;
+  hipLaunchKernelGGL(seg_head_dice_fwd_kernel<true>, dim3(syn_grid(nvox, SHD_TILE, head_grid())), dim3(256),
+                     ShdFwdLds(C, N, true, true).total * sizeof(float), (hipStream_t)stream, x, nvox, C, stats, gamma, beta, eps,
+                     w, b, N, seg, lut, lut_n, probs, sums, mask, boundary_weights);
+  SYN_CHECK_LAUNCH();
+  return SYNTHSR_OK;
+}
+
+int synthsr_seg_boundary_mask(const int32_t* seg, const int* shape, const int32_t* lut, int lut_n, int N, int boundary_dist,
+                              int skip_background, uint64_t* mask, synthsr_stream_t stream) {
+  if (!seg || !shape || !lut || !mask || lut_n < 1 || N < 1 || N > SEG_MAXN || boundary_dist < 1 || boundary_dist > SBM_MAXD ||
+      shape[0] < 1 || shape[1] < 1 || shape[2] < 1 || ((uintptr_t)mask % 8) != 0)
+    return SYNTHSR_EINVAL;
+  const int64_t tiles = syn_cdiv(shape[0], SBM_TZ) * syn_cdiv(shape[1], SBM_TY) * syn_cdiv(shape[2], SBM_TX);
+  if (tiles > INT32_MAX) return SYNTHSR_EINVAL;
+  hipLaunchKernelGGL(seg_boundary_mask_kernel, dim3(syn_grid(tiles, 1, 256 * 32)), dim3(256), 0, (hipStream_t)stream, seg,
+                     shape[0], shape[1], shape[2], lut, lut_n, N, boundary_dist, (skip_background && N > 1) ? 1 : 0, mask);
   SYN_CHECK_LAUNCH();
   return SYNTHSR_OK;
 }
@@ -2618,9 +2774,24 @@ int synthsr_seg_head_dice_bwd(const float* probs, const int32_t* seg, const int3
   if (!probs || !seg || !lut || !x || !stats || !gamma || !beta || !w || !sums || !dbn || !dw || !db ||
       !shd_ok(nvox, C, N, lut_n, x))
     return SYNTHSR_EINVAL;
-  hipLaunchKernelGGL(seg_head_dice_bwd_kernel, dim3(syn_grid(nvox, SHD_TILE, head_grid())), dim3(256),
+  hipLaunchKernelGGL(seg_head_dice_bwd_kernel<false>, dim3(syn_grid(nvox, SHD_TILE, head_grid())), dim3(256),
                      ShdBwdLds(C, N).total * sizeof(float), (hipStream_t)stream, probs, seg, lut, lut_n, x, nvox, C, N, stats, gamma,
-                     beta, eps, w, sums, scale, dbn, dw, db);
+                     beta, eps, w, sums, scale, dbn, dw, db, (const uint64_t*)nullptr, 0.f, (const float*)nullptr);
+  SYN_CHECK_LAUNCH();
+  return SYNTHSR_OK;
+}
+
+int synthsr_seg_head_dice_bwd_weighted(const float* probs, const int32_t* seg, const int32_t* lut, int lut_n, const float* x,
+                                       int64_t nvox, int C, int N, const float* stats, const float* gamma, const float* beta,
+                                       float eps, const float* w, const float* sums, const uint64_t* mask, float boundary_weights,
+                                       const float* class_weights, float scale, float* dbn, float* dw, float* db,
+                                       synthsr_stream_t stream) {
+  if (!probs || !seg || !lut || !x || !stats || !gamma || !beta || !w || !sums || !class_weights || !dbn || !dw || !db ||
+      !shd_ok(nvox, C, N, lut_n, x) || ((uintptr_t)mask % 8) != 0)
+    return SYNTHSR_EINVAL;
+  hipLaunchKernelGGL(seg_head_dice_bwd_kernel<true>, dim3(syn_grid(nvox, SHD_TILE, head_grid())), dim3(256),
+                     ShdBwdLds(C, N, true).total * sizeof(float), (hipStream_t)stream, probs, seg, lut, lut_n, x, nvox, C, N,
+                     stats, gamma, beta, eps, w, sums, scale, dbn, dw, db, mask, boundary_weights, class_weights);
   SYN_CHECK_LAUNCH();
   return SYNTHSR_OK;
 }

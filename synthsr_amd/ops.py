@@ -840,31 +840,97 @@ def _seg_head_dice_args(what, x, w, b, seg, lut, probs):
     return C, nvox, N
 
 
-def seg_head_dice_fwd(x, stats, gamma, beta, w, b, seg, lut, probs, sums, eps=BN_EPS):
+BOUNDARY_DIST_MAX = 5   # the integer boundary rule of seg_boundary_mask is the reference's float rule up to here
+
+
+def check_boundary_dist(boundary_dist):
+    """the boundary distance of the weighted soft Dice as an int in 1 .. 5, or ValueError"""
+    if isinstance(boundary_dist, bool) or int(boundary_dist) != boundary_dist or not 1 <= int(boundary_dist) <= BOUNDARY_DIST_MAX:
+        raise ValueError('boundary_dist should be an integer from 1 to %d (got %r): beyond it the window holds 3333 voxels or '
+                         'more and the integer boundary rule no longer equals the float rule it restates'
+                         % (BOUNDARY_DIST_MAX, boundary_dist))
+    return int(boundary_dist)
+
+
+def seg_boundary_mask(seg, lut, N, boundary_dist=3, skip_background=True, mask=None):
+    """mask [d0,d1,d2] (int64 holding 64 bits; made here unless given) of the label map seg [d0,d1,d2] (int32 label VALUES):
+    bit n of mask[v] = voxel v is a boundary voxel of head channel n, DiceLoss's [avg > 0][avg < 1/3 - 1e-4] with avg the
+    'same' average pooling of the one-hot of lut[seg] over (2 boundary_dist + 1)^3 (ext/lab2im/layers.py:1349-1353),
+    evaluated exactly in integers.  skip_background (and N > 1): bit 0 stays clear.  1 <= boundary_dist <= 5, N <= 64"""
+    if seg.dim() != 3 or seg.dtype != torch.int32 or lut.dtype != torch.int32 or lut.numel() < 1:
+        raise ValueError('seg_boundary_mask takes an int32 label map [d0, d1, d2] and an int32 lookup table')
+    d = check_boundary_dist(boundary_dist)
+    if not 1 <= int(N) <= 64:
+        raise ValueError('seg_boundary_mask: one mask bit per head channel, N <= 64 (got %r)' % (N,))
+    if mask is None:
+        mask = torch.empty(seg.shape, dtype=torch.int64, device=seg.device)
+    if mask.dtype != torch.int64 or mask.numel() != seg.numel():
+        raise ValueError('seg_boundary_mask: the mask holds one int64 per voxel')
+    _lib.check(_L().synthsr_seg_boundary_mask(_lib.ptr(seg), _lib.i3(seg.shape), _lib.ptr(lut), int(lut.numel()), int(N), d,
+                                              int(bool(skip_background)), _lib.ptr(mask), _lib.stream()), 'seg_boundary_mask')
+    return mask
+
+
+def _seg_dice_mask(what, mask, nvox):
+    if mask is not None and (mask.dtype != torch.int64 or mask.numel() != nvox):
+        raise ValueError('%s: the boundary mask holds one int64 per voxel (seg_boundary_mask)' % what)
+
+
+def seg_head_dice_fwd(x, stats, gamma, beta, w, b, seg, lut, probs, sums, eps=BN_EPS, mask=None, boundary_weights=0.,
+                      class_weights=None):
     """trainable softmax head + soft Dice, forward: probs [nvox, N] = softmax(bn(x) @ w + b) written and sums [2N] (zeroed
     here) <- the Dice numerators 2 sum gt p | denominators sum gt^2 + p^2, gt = one-hot of lut[seg] (label values outside
     the table or mapped to -1: no class).  x [d0,d1,d2,C] with C <= 64, N <= 64.  loss = mean(1 - (top + 1e-7) / (bottom +
-    1e-7))"""
+    1e-7)).
+    Weighted (a `mask` of seg_boundary_mask and / or `class_weights` other than None): every term of voxel v and class n
+    counts 1 + boundary_weights * (bit n of mask[v]) times, and sums is [3N]: numerators | denominators | the weighted
+    volumes sum w gt that dynamic class weights are the inverse of.  The class weights themselves enter the loss,
+    sum_n c_n (1 - dice_n), and the backward pass only"""
     C, nvox, N = _seg_head_dice_args('seg_head_dice_fwd', x, w, b, seg, lut, probs)
-    if sums.numel() != 2 * N:
-        raise ValueError('seg_head_dice_fwd: sums should hold 2 N = %d values, holds %d' % (2 * N, sums.numel()))
+    weighted = mask is not None or class_weights is not None
+    rows = 3 if weighted else 2
+    if sums.numel() != rows * N:
+        raise ValueError('seg_head_dice_fwd: sums should hold %d N = %d values, holds %d' % (rows, rows * N, sums.numel()))
     sums.zero_()
-    _lib.check(_L().synthsr_seg_head_dice_fwd(_lib.ptr(x), nvox, C, _lib.ptr(stats), _lib.ptr(gamma), _lib.ptr(beta), eps,
-                                              _lib.ptr(w), _lib.ptr(b), N, _lib.ptr(seg), _lib.ptr(lut), int(lut.numel()),
-                                              _lib.ptr(probs), _lib.ptr(sums), _lib.stream()), 'seg_head_dice_fwd')
+    if not weighted:
+        _lib.check(_L().synthsr_seg_head_dice_fwd(_lib.ptr(x), nvox, C, _lib.ptr(stats), _lib.ptr(gamma), _lib.ptr(beta), eps,
+                                                  _lib.ptr(w), _lib.ptr(b), N, _lib.ptr(seg), _lib.ptr(lut), int(lut.numel()),
+                                                  _lib.ptr(probs), _lib.ptr(sums), _lib.stream()), 'seg_head_dice_fwd')
+        return probs
+    _seg_dice_mask('seg_head_dice_fwd', mask, nvox)
+    _lib.check(_L().synthsr_seg_head_dice_fwd_weighted(_lib.ptr(x), nvox, C, _lib.ptr(stats), _lib.ptr(gamma), _lib.ptr(beta),
+                                                       eps, _lib.ptr(w), _lib.ptr(b), N, _lib.ptr(seg), _lib.ptr(lut),
+                                                       int(lut.numel()), _lib.ptr(mask), float(boundary_weights),
+                                                       _lib.ptr(probs), _lib.ptr(sums), _lib.stream()), 'seg_head_dice_fwd')
     return probs
 
 
-def seg_head_dice_bwd(probs, seg, lut, x, stats, gamma, beta, w, sums, dbn, dw, db, scale=1.0, eps=BN_EPS):
+def seg_head_dice_bwd(probs, seg, lut, x, stats, gamma, beta, w, sums, dbn, dw, db, scale=1.0, eps=BN_EPS, mask=None,
+                      boundary_weights=0., class_weights=None):
     """backward of scale * Dice through softmax and head: dbn [d0,d1,d2,C] (gradient w.r.t. the last BatchNorm's output)
-    written, dw [C, N] and db [N] accumulated; probs / sums as seg_head_dice_fwd left them"""
+    written, dw [C, N] and db [N] accumulated; probs / sums as seg_head_dice_fwd left them.
+    Weighted (`mask` and / or `class_weights` given, as in seg_head_dice_fwd; sums [3N]): the gradient of
+    scale * sum_n c_n (1 - dice_n), c = class_weights [N] (float32, device; None: 1 / N each), constants of the step"""
     C, nvox, N = _seg_head_dice_args('seg_head_dice_bwd', x, w, db, seg, lut, probs)
-    if sums.numel() != 2 * N or dbn.numel() != x.numel() or dw.numel() != C * N or dbn.dtype != torch.float32:
-        raise ValueError('seg_head_dice_bwd: sums [2 N], dbn like x (float32) and dw [C, N] are needed')
-    _lib.check(_L().synthsr_seg_head_dice_bwd(_lib.ptr(probs), _lib.ptr(seg), _lib.ptr(lut), int(lut.numel()), _lib.ptr(x), nvox,
-                                              C, N, _lib.ptr(stats), _lib.ptr(gamma), _lib.ptr(beta), eps, _lib.ptr(w),
-                                              _lib.ptr(sums), float(scale), _lib.ptr(dbn), _lib.ptr(dw), _lib.ptr(db),
-                                              _lib.stream()), 'seg_head_dice_bwd')
+    weighted = mask is not None or class_weights is not None
+    if sums.numel() != (3 if weighted else 2) * N or dbn.numel() != x.numel() or dw.numel() != C * N or dbn.dtype != torch.float32:
+        raise ValueError('seg_head_dice_bwd: sums [2 N] (weighted: [3 N]), dbn like x (float32) and dw [C, N] are needed')
+    if not weighted:
+        _lib.check(_L().synthsr_seg_head_dice_bwd(_lib.ptr(probs), _lib.ptr(seg), _lib.ptr(lut), int(lut.numel()), _lib.ptr(x),
+                                                  nvox, C, N, _lib.ptr(stats), _lib.ptr(gamma), _lib.ptr(beta), eps, _lib.ptr(w),
+                                                  _lib.ptr(sums), float(scale), _lib.ptr(dbn), _lib.ptr(dw), _lib.ptr(db),
+                                                  _lib.stream()), 'seg_head_dice_bwd')
+        return dbn
+    _seg_dice_mask('seg_head_dice_bwd', mask, nvox)
+    if class_weights is None:
+        class_weights = torch.full((N,), 1.0 / N, dtype=torch.float32, device=x.device)
+    if class_weights.dtype != torch.float32 or class_weights.numel() != N or class_weights.device != x.device:
+        raise ValueError('seg_head_dice_bwd: class_weights is a float32 device tensor of N = %d values' % N)
+    _lib.check(_L().synthsr_seg_head_dice_bwd_weighted(_lib.ptr(probs), _lib.ptr(seg), _lib.ptr(lut), int(lut.numel()),
+                                                       _lib.ptr(x), nvox, C, N, _lib.ptr(stats), _lib.ptr(gamma), _lib.ptr(beta),
+                                                       eps, _lib.ptr(w), _lib.ptr(sums), _lib.ptr(mask), float(boundary_weights),
+                                                       _lib.ptr(class_weights), float(scale), _lib.ptr(dbn), _lib.ptr(dw),
+                                                       _lib.ptr(db), _lib.stream()), 'seg_head_dice_bwd')
     return dbn
 
 

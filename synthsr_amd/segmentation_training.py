@@ -40,11 +40,12 @@ class SegmentationTrainer(Trainer):
     """generator + softmax-headed U-Net + soft Dice + Adam; the sample, the optimizer step and the moving statistics are
     Trainer's"""
 
-    def __init__(self, brain_generator, net, lut, lr=1e-4, lr_decay=0.0, fixed_sample=False):
+    def __init__(self, brain_generator, net, lut, lr=1e-4, lr_decay=0.0, fixed_sample=False, dice=None):
         import torch
         Trainer.__init__(self, brain_generator, net, lr, lr_decay)
         self.lut = torch.as_tensor(np.asarray(lut, dtype=np.int32)).to(net.device)
         self.fixed_sample = bool(fixed_sample)
+        self.dice = dict(dice or {})   # the weights of UNet3D.loss_dice (dice_settings); empty: the plain soft Dice
         self._fixed = None
 
     def step(self, model_inputs=None, draws=None, label_index=None):
@@ -65,7 +66,7 @@ class SegmentationTrainer(Trainer):
                 self._fixed = x, seg = target.clone(), seg.clone()
         net.set_batch(1)
         with ops.trace_range('forward + loss'):
-            loss = net.loss_dice(x, seg, self.lut)
+            loss = net.loss_dice(x, seg, self.lut, **self.dice)
         with ops.trace_range('backward'):
             net.backward()
         with ops.trace_range('optimizer'):
@@ -90,6 +91,29 @@ def check_scope(batchsize=1, dtype='f32', images_dir=None, fs_header_segnet=Fals
         raise NotImplementedError('training_segmentation trains in the generator\'s frame: fs_header_segnet is not supported')
 
 
+def dice_settings(n_labels, dice_class_weights=None, dice_boundary_weights=0., dice_boundary_dist=3,
+                  dice_skip_background=True):
+    """the four Dice settings of training_segmentation as keywords of UNet3D.loss_dice, checked: class weights None, -1
+    (dynamic; '-1' from a command line), a sequence or the path of a .npy of n_labels finite values >= 0 that are not all zero;
+    boundary weights a finite number >= 0; a boundary distance of 1 .. 5"""
+    from .ops import check_boundary_dist
+    from .unet import dice_class_weights as normalised
+    cw = dice_class_weights
+    if isinstance(cw, str):
+        cw = None if cw in ('', 'None') else (-1 if cw.strip() == '-1' else np.load(cw))
+    if cw is not None and not (np.ndim(cw) == 0 and cw == -1):
+        if np.ndim(cw) == 0:
+            raise ValueError('dice_class_weights: None, -1 (dynamic), a sequence or a .npy path (got %r)' % (dice_class_weights,))
+        cw = normalised(cw, n_labels)
+    elif cw is not None:
+        cw = -1
+    bw = float(dice_boundary_weights)
+    if not bw >= 0. or not np.isfinite(bw):
+        raise ValueError('dice_boundary_weights should be a finite number >= 0 (got %r)' % (dice_boundary_weights,))
+    return dict(class_weights=cw, boundary_weights=bw, boundary_dist=check_boundary_dist(dice_boundary_dist),
+                skip_background=bool(dice_skip_background))
+
+
 def training_segmentation(labels_dir, model_dir, prior_means, prior_stds, path_generation_labels, segmentation_label_list,
                           prior_distributions='normal', images_dir=None, path_generation_classes=None, FS_sort=True,
                           batchsize=1, input_channels=True, output_channel=0, target_res=None, output_shape=None,
@@ -100,13 +124,19 @@ def training_segmentation(labels_dir, model_dir, prior_means, prior_stds, path_g
                           bias_shape_factor=0.03125, n_levels=5, nb_conv_per_level=2, conv_size=3, unet_feat_count=24,
                           feat_multiplier=2, dropout=0, activation='elu', lr=1e-4, lr_decay=0, epochs=100,
                           steps_per_epoch=1000, checkpoint=None, seed=0, verbose=True, dtype='f32', deterministic=False,
-                          fs_header_segnet=False, fixed_sample=False, step_losses=None):
+                          fs_header_segnet=False, fixed_sample=False, step_losses=None, dice_class_weights=None,
+                          dice_boundary_weights=0., dice_boundary_dist=3, dice_skip_background=True):
     """Generator arguments: those of synthsr_amd.training.training, same names and defaults.  `segmentation_label_list`
     (array or path): the label values the network predicts, in head-channel order; label values of the maps that are not
     listed have no class (an all-zero ground-truth row).  `output_channel`: ONE index, the synthetic channel the network is
     trained on (the generator's regression target, as is).  `fixed_sample`: every step trains on the first sample drawn
     (overfitting tests).  `step_losses` (optional list): receives every step's loss as a float, at the cost of a host
-    synchronisation per step.  Returns the network."""
+    synchronisation per step.
+    The weights of the reference's DiceLoss (UNet3D.loss_dice), all off by default: `dice_class_weights` None, -1 (dynamic:
+    the inverse of each label's volume in the sample; a label that the sample does not hold gets weight 0 where the reference
+    divides by zero), a sequence or the path of a .npy with one value >= 0 per entry of segmentation_label_list;
+    `dice_boundary_weights` (bonus weight of voxels within `dice_boundary_dist`, 1 .. 5, of a label's boundary) and
+    `dice_skip_background` (no bonus for the first label of the list).  Returns the network."""
     check_scope(batchsize, dtype, images_dir, fs_header_segnet, int(os.environ.get('WORLD_SIZE', '1')))
     if deterministic:  # process-wide switch: on for the duration of this call, previous setting restored on the way out
         from . import ops as _ops
@@ -128,6 +158,7 @@ def training_segmentation(labels_dir, model_dir, prior_means, prior_stds, path_g
         raise Exception('indices in output_channel cannot be greater than the total number of channels')
     lut = segmentation_lut(segmentation_label_list)
     n_seg = int((lut >= 0).sum())
+    dice = dice_settings(n_seg, dice_class_weights, dice_boundary_weights, dice_boundary_dist, dice_skip_background)
 
     generation_labels, n_neutral_labels = volumes.get_list_labels(label_list=path_generation_labels, labels_dir=labels_dir,
                                                                   FS_sort=FS_sort)
@@ -160,7 +191,7 @@ def training_segmentation(labels_dir, model_dir, prior_means, prior_stds, path_g
             init_epoch = int(os.path.basename(checkpoint)[:3])
         except ValueError:
             init_epoch = 0
-    trainer = SegmentationTrainer(brain_generator, net, lut, lr, lr_decay, fixed_sample=fixed_sample)
+    trainer = SegmentationTrainer(brain_generator, net, lut, lr, lr_decay, fixed_sample=fixed_sample, dice=dice)
     step = trainer.step
     if step_losses is not None:
         def step():

@@ -18,6 +18,19 @@ import torch
 from . import ops
 
 
+def dice_class_weights(weights, n_labels):
+    """fixed class weights of the weighted soft Dice as a tuple of n_labels floats that sum to 1 (DiceLoss normalises them,
+    ext/lab2im/layers.py:1373): n_labels finite values >= 0, not all zero; anything else raises ValueError"""
+    w = np.asarray(weights, dtype=np.float64).reshape(-1)
+    if w.size != n_labels:
+        raise ValueError('class_weights should hold one value per label: %d, not %d' % (n_labels, w.size))
+    if not np.all(np.isfinite(w)) or np.any(w < 0):
+        raise ValueError('class_weights should be finite and >= 0 (got %s)' % (w.tolist(),))
+    if not w.sum() > 0:
+        raise ValueError('class_weights are all zero')
+    return tuple(float(v) for v in w / w.sum())
+
+
 class UNet3D:
     def __init__(self, nb_features, input_shape, nb_levels, conv_size, nb_labels, name='unet', prefix=None,
                  feat_mult=1, nb_conv_per_level=1, batch_norm=None, activation='elu', device=None, seed=0,
@@ -354,7 +367,7 @@ class UNet3D:
 
     # ------------------------------------------------------------------ buffers
     _F32_BUFS = ('loss', 'dpred', 'pred', 'loss_unused', 'zero_t', 'probs', 'dwc', 'head_ab', 'dice_sums', 'probs_avg',
-                 'label_map', 'dx_input_f32')
+                 'label_map', 'dx_input_f32', 'dice_sums_w', 'dice_class_weights')
 
     def buf(self, key, shape):
         """persistent scratch tensor: activations / activation gradients in the network's dtype, the head's outputs,
@@ -695,14 +708,31 @@ class UNet3D:
         """forward + unet_likelihood + L1 (SynthSR/metrics_model.py:102-104). Returns (loss tensor[1], pred|None)"""
         return self.loss(x, target, 'l1', None, residual, res_stride, res_off, want_pred)
 
-    def loss_dice(self, x, seg, lut):
+    def loss_dice(self, x, seg, lut, class_weights=None, boundary_weights=0., boundary_dist=3, skip_background=True):
         """training step of a softmax-headed (segmentation) network: forward in training mode + unet_likelihood + softmax +
         soft Dice (ext/lab2im/layers.py:1343-1376, enable_checks=False) against the label map `seg` (int32 [d0,d1,d2] label
         VALUES) in one fused head kernel.  lut (int32, device): label value -> head channel or -1; a voxel whose label is
         outside the table or maps to -1 has an all-zero ground truth.  Returns the loss as a 1-element device tensor;
-        posteriors, Dice sums and the label map are kept for backward().  fp32, batch 1."""
+        posteriors, Dice sums and the label map are kept for backward().  fp32, batch 1.
+        DiceLoss's weights (layers.py:1347-1374), all off by default:
+          class_weights     None: the mean over the labels.  A sequence of nb_labels values >= 0 (not all zero): the loss is
+                            sum_n c_n (1 - dice_n), c = class_weights / their sum.  -1 ("dynamic"): c_n ~ the inverse of label
+                            n's volume in this ground truth (its boundary-weighted volume with boundary_weights).  Where the
+                            reference divides by zero for a label that the sample does not hold (a NaN loss), such a label
+                            gets c_n = 0 here and the others are normalised; a sample without any label: loss 0, no gradient.
+          boundary_weights  bonus b > 0: voxel v counts 1 + b times in the sums of label n where it lies within
+                            boundary_dist (1 .. 5) of label n's boundary (ops.seg_boundary_mask, computed once per call)
+          skip_background   no bonus for head channel 0"""
         if self.final_pred_activation != 'softmax':
             raise ValueError('loss_dice() is for softmax heads; use loss() for a linear head')
+        bw = float(boundary_weights)
+        if not bw >= 0. or bw == float('inf'):
+            raise ValueError('boundary_weights should be a finite number >= 0 (got %r)' % (boundary_weights,))
+        if bw:
+            boundary_dist = ops.check_boundary_dist(boundary_dist)
+        dynamic = isinstance(class_weights, (int, float)) and class_weights == -1
+        if class_weights is not None and not dynamic:
+            class_weights = dice_class_weights(class_weights, self.nb_labels)
         if self.bf16:
             raise NotImplementedError('the soft-Dice training head is fp32 only (dtype=%r)' % 'bf16')
         if self.batch != 1:
@@ -715,13 +745,38 @@ class UNet3D:
         if seg.numel() != nvox:
             raise ValueError('label map of %d voxels for a prediction of %d' % (seg.numel(), nvox))
         probs = self.buf('probs', [nvox, N])
-        sums = self.buf('dice_sums', [2 * N])
+        self.loss_buf = self.buf('loss', [1])
+        if class_weights is None and not bw:   # the plain soft Dice: the unweighted kernels
+            sums = self.buf('dice_sums', [2 * N])
+            seg = seg.reshape(-1)
+            ops.seg_head_dice_fwd(low, self._stats(bn), self.view(bn['gamma']), self.view(bn['beta']),
+                                  self.view(self.head['w']), self.view(self.head['b']), seg, lut, probs, sums)
+            self._dice = (probs, sums, seg, lut)
+            torch.mean(1.0 - (sums[:N] + 1e-7) / (sums[N:] + 1e-7), 0, keepdim=True, out=self.loss_buf)
+            return self.loss_buf
+        mask = None
+        if bw:   # 8 bytes per voxel, written once here and read by the two head kernels
+            if getattr(self, '_dice_mask', None) is None or self._dice_mask.numel() != nvox:
+                self._dice_mask = torch.empty(nvox, dtype=torch.int64, device=self.device)
+            mask = ops.seg_boundary_mask(seg.reshape(low.shape[:3]), lut, N, boundary_dist, skip_background,
+                                         mask=self._dice_mask)
+        sums = self.buf('dice_sums_w', [3 * N])
         seg = seg.reshape(-1)
         ops.seg_head_dice_fwd(low, self._stats(bn), self.view(bn['gamma']), self.view(bn['beta']), self.view(self.head['w']),
-                              self.view(self.head['b']), seg, lut, probs, sums)
-        self._dice = (probs, sums, seg, lut)
-        self.loss_buf = self.buf('loss', [1])
-        torch.mean(1.0 - (sums[:N] + 1e-7) / (sums[N:] + 1e-7), 0, keepdim=True, out=self.loss_buf)
+                              self.view(self.head['b']), seg, lut, probs, sums, mask=mask, boundary_weights=bw, class_weights=True)
+        c = self.buf('dice_class_weights', [N])
+        if dynamic:   # the inverse of the (weighted) volumes; a label without a voxel: 0.  All on the device
+            vol = sums[2 * N:]
+            inv = torch.where(vol > 0, 1.0 / vol.clamp_min(1e-30), torch.zeros_like(vol))
+            torch.div(inv, inv.sum().clamp_min(1e-30), out=c)
+        elif class_weights is None:
+            c.fill_(1.0 / N)
+        else:   # fixed weights: uploaded when they change, not every step
+            if getattr(self, '_dice_fixed', (None, None))[0] != class_weights:
+                self._dice_fixed = (class_weights, torch.tensor(class_weights, dtype=torch.float32, device=self.device))
+            c.copy_(self._dice_fixed[1])
+        self._dice = (probs, sums, seg, lut, mask, bw, c)
+        torch.sum(c * (1.0 - (sums[:N] + 1e-7) / (sums[N:2 * N] + 1e-7)), 0, keepdim=True, out=self.loss_buf)
         return self.loss_buf
 
     def predict(self, x):
@@ -877,11 +932,14 @@ class UNet3D:
             if getattr(self, '_dice', None) is None:
                 raise RuntimeError('backward() on a softmax head needs loss_dice() first (after predict_probs() the network '
                                    'is frozen: backward_input())')
-            probs, sums, seg, lut = self._dice
+            probs, sums, seg, lut = self._dice[:4]
+            weights = {}
+            if len(self._dice) > 4:   # the weighted Dice: the mask and the class weights of loss_dice()
+                weights = dict(zip(('mask', 'boundary_weights', 'class_weights'), self._dice[4:]))
             dbn = self.buf('dbn_head', list(low.shape))
             ops.seg_head_dice_bwd(probs, seg, lut, low, self._stats(bn), self.view(bn['gamma']), self.view(bn['beta']),
                                   self.view(self.head['w']), sums, dbn, self.view(self.head['w'], G),
-                                  self.view(self.head['b'], G))
+                                  self.view(self.head['b'], G), **weights)
             return self._backward_body(dbn, on_grad_ready)
         # the gradient w.r.t. the last BatchNorm output is rank-1 (dpred[v] * w_head[c]): it is neither stored nor
         # reduced; head_bwd emits that BN's backward sums and the first ELU backward forms it on the fly

@@ -2,7 +2,10 @@
 """time of the two soft-Dice head kernels (synthsr_seg_head_dice_fwd / _bwd) at the benchmark size next to their compulsory
 HBM traffic, and of one segmentation training step next to the regression step of the same network, in one process:
 
-    python tools/seg_training_bench.py [--size 160] [--C 24] [--N 33] > profiles/seg_training_kernels.txt"""
+    python tools/seg_training_bench.py [--size 160] [--C 24] [--N 33] > profiles/seg_training_kernels.txt
+
+With --dice_class_weights -1 and / or --dice_boundary_weights B the weighted forms are timed (and the boundary-mask kernel, on a
+label map of 8^3-voxel blocks: per-voxel random labels put every class into every window, which no anatomy does)."""
 import argparse
 import os
 import sys
@@ -38,7 +41,14 @@ def main():
     ap.add_argument('--C', type=int, default=24)
     ap.add_argument('--N', type=int, default=33)
     ap.add_argument('--levels', type=int, default=5)
+    ap.add_argument('--dice_class_weights', type=str, default=None, help='-1 (dynamic) or a .npy of N values')
+    ap.add_argument('--dice_boundary_weights', type=float, default=0.)
+    ap.add_argument('--dice_boundary_dist', type=int, default=3)
+    ap.add_argument('--dice_no_skip_background', dest='dice_skip_background', action='store_false')
     a = ap.parse_args()
+    from synthsr_amd.segmentation_training import dice_settings
+    dice = dice_settings(a.N, a.dice_class_weights, a.dice_boundary_weights, a.dice_boundary_dist, a.dice_skip_background)
+    weighted = dice['class_weights'] is not None or dice['boundary_weights'] > 0
     S, C, N = a.size, a.C, a.N
     nvox = S ** 3
     g = torch.Generator().manual_seed(0)
@@ -48,15 +58,35 @@ def main():
     w, b = (torch.randn(C, N, generator=g) * .3).cuda(), torch.zeros(N).cuda()
     lut = torch.arange(N, dtype=torch.int32).cuda()
     seg = torch.randint(0, N + 3, (nvox,), generator=g, dtype=torch.int32).cuda()
-    probs, sums = torch.empty(nvox, N).cuda(), torch.empty(2 * N).cuda()
+    probs, sums = torch.empty(nvox, N).cuda(), torch.empty((3 if weighted else 2) * N).cuda()
+    mask, kw_w = None, {}
+    if weighted:
+        blocks = torch.randint(0, N + 3, ((S + 7) // 8,) * 3, generator=g, dtype=torch.int32)
+        seg = blocks.repeat_interleave(8, 0).repeat_interleave(8, 1).repeat_interleave(8, 2)[:S, :S, :S].contiguous().cuda()
+        cw = torch.full((N,), 1.0 / N).cuda()   # (the kernels' time does not depend on the values)
+        if dice['boundary_weights'] > 0:
+            mask = torch.empty(nvox, dtype=torch.int64).cuda()
+        kw_w = dict(mask=mask, boundary_weights=dice['boundary_weights'], class_weights=cw)
     dbn, dw, db = torch.empty_like(x), torch.zeros(C, N).cuda(), torch.zeros(N).cuda()
     print('soft-Dice head kernels, %d^3 voxels, C = %d, N = %d, fp32 (median / min / max of 20 launches, HIP events)' % (S, C, N))
     fwd_bytes = nvox * 4 * (C + 1 + N)           # x + label map read, probs written
     bwd_bytes = nvox * 4 * (N + 1 + C + C)       # probs + label map + x read, dbn written
-    for name, fn, nbytes in (
-            ('seg_head_dice_fwd', lambda: ops.seg_head_dice_fwd(x, stats, gamma, beta, w, b, seg, lut, probs, sums), fwd_bytes),
-            ('seg_head_dice_bwd', lambda: ops.seg_head_dice_bwd(probs, seg, lut, x, stats, gamma, beta, w, sums, dbn, dw, db),
-             bwd_bytes)):
+    rows = []
+    if mask is not None:   # label map read, mask written; then the two head kernels read it
+        rows.append(('seg_boundary_mask', lambda: ops.seg_boundary_mask(seg.view(S, S, S), lut, N, dice['boundary_dist'],
+                                                                        dice['skip_background'], mask=mask), nvox * 12))
+        fwd_bytes += nvox * 8
+        bwd_bytes += nvox * 8
+    seg = seg.reshape(-1)
+    rows += [('seg_head_dice_fwd', lambda: ops.seg_head_dice_fwd(x, stats, gamma, beta, w, b, seg, lut, probs, sums, **kw_w),
+              fwd_bytes),
+             ('seg_head_dice_bwd', lambda: ops.seg_head_dice_bwd(probs, seg, lut, x, stats, gamma, beta, w, sums, dbn, dw, db,
+                                                                 **kw_w), bwd_bytes)]
+    if weighted:
+        print('weighted soft Dice: class weights %s, boundary weights %g within %d voxels' % (
+            'dynamic' if dice['class_weights'] == -1 else ('fixed' if dice['class_weights'] is not None else 'none'),
+            dice['boundary_weights'], dice['boundary_dist']))
+    for name, fn, nbytes in rows:
         med, lo, hi = timed(fn)
         floor = nbytes / HBM * 1e3
         print('%-18s %.3f ms (%.3f .. %.3f)   compulsory %.1f MB = %.3f ms at 8 TB/s   -> %.0f %% of the HBM floor rate'
@@ -70,7 +100,7 @@ def main():
     regnet = UNet3D(C, [S, S, S, 1], a.levels, 3, 1, final_pred_activation='linear', **kw)
 
     def seg_step():
-        segnet.loss_dice(img, seg, lut)
+        segnet.loss_dice(img, seg, lut, **dice)
         segnet.backward()
         segnet.adam_step(1e-4)
         segnet.update_moving_stats()
