@@ -675,6 +675,21 @@ int synthsr_seg_head_tta_argmax(const float* x, const int* shape, int C, const f
 int synthsr_seg_label_counts(const int32_t* a, const int32_t* b, int64_t nvox, const int32_t* lut, int lut_n, int N,
                              uint64_t* counts, synthsr_stream_t stream);
 
+/* --- surface distances of two label maps: exact squared Euclidean distances, in integers ---------------------------------
+ * a, b [shape[0]][shape[1]][shape[2]] label maps, lut as above.  Voxel v of class k (the rule of label_counts) is a SURFACE
+ * voxel of class k of its map when one of its six face neighbours lies outside the volume or has another class (or none);
+ * a voxel without a class is never one.  d2_ab, d2_ba [nvox] int32, every element written:
+ *   d2_ab[v] = min over the surface voxels u of class k in b of |v - u|^2 (voxel units)  for v a surface voxel of class k in a,
+ *              INT32_MAX when b has no surface voxel of class k, -1 when v is no surface voxel of a;  d2_ba: a and b exchanged.
+ * All arithmetic is int32: the result does not depend on the launch order.  Limits: every side 1 .. 1024, 1 <= N <= 64.
+ * workspace: synthsr_seg_surface_workspace_bytes(shape, N) bytes of device memory, 16-byte aligned, owned by the caller (the
+ * library allocates nothing); its contents need no initialisation and mean nothing afterwards.  A NULL pointer, a side or N
+ * outside the limits, a misaligned or too small workspace return SYNTHSR_EINVAL before any launch (workspace_bytes: -1). */
+int64_t synthsr_seg_surface_workspace_bytes(const int* shape, int N);
+int synthsr_seg_surface_dist2(const int32_t* a, const int32_t* b, const int* shape, const int32_t* lut, int lut_n, int N,
+                              int32_t* d2_ab, int32_t* d2_ba, void* workspace, int64_t workspace_bytes,
+                              synthsr_stream_t stream);
+
 /* --- a frozen or inference softmax-headed U-Net in bf16 ------------------------------------------------------------------
  * The feature map x [nvox][C] is bf16 (8-byte aligned: one channel quad per vector load); BatchNorm statistics, gamma / beta,
  * the head's fp32 master weights w / b, posteriors, prev and the Dice sums stay fp32, so the arithmetic on a given bf16 x is

@@ -1,17 +1,20 @@
 #!/usr/bin/env python
 """Segments volumes with a network trained by scripts/training_segmentation.py and, given ground-truth label maps, scores
-the result with the per-label Dice coefficient.
+the result with the per-label Dice coefficient and the distances between the surfaces of the two label maps.
 
     python scripts/predict_segmentation.py <path_images> <path_segmentations> --model M.npz|M.h5 --labels L.npy
                                            [--lr_pairs P.npy] [--posteriors <path>] [--disable_flipping]
                                            [--n_levels 5 --conv_per_level 2 --unet_feat 24 --feat_mult 2 --activation elu]
                                            [--dtype f32|bf16]
-                                           [--truth <path> [--scores S.npy|S.csv]]
+                                           [--truth <path> [--scores S.npy|S.csv]
+                                                            [--surface_scores D.npy|D.csv [--surface_percentile 95]]]
 
 <path_images>, <path_segmentations> (and --posteriors, --truth) are all single files or all folders; label maps written
 into a folder carry the suffix _seg.  --labels: the label values in head-channel order (what training_segmentation took as
 segmentation_label_list); --lr_pairs: a [K, 2] array of (left value, right value) pairs whose channels are swapped in the
-flipped pass of the test-time augmentation."""
+flipped pass of the test-time augmentation.  --surface_scores: per label the Hausdorff distance, the --surface_percentile-th
+percentile distance and the mean distance between the surfaces of segmentation and ground truth, in mm (label maps are written
+at 1 mm): .npy [n_volumes, 3, N] in that order; .csv a header of label values, then three rows per volume in that order."""
 import os
 import sys
 from argparse import ArgumentParser
@@ -39,7 +42,25 @@ def build_parser():
                    help='arithmetic of the network: bf16 = bf16 activations and packed weights, fp32 head and posteriors')
     p.add_argument('--truth', default=None, help='ground-truth label map (or folder, sorted like the images): score with Dice')
     p.add_argument('--scores', default=None, help='write the per-label Dice table here (.npy or .csv); needs --truth')
+    p.add_argument('--surface_scores', default=None,
+                   help='write the per-label surface distances (Hausdorff, percentile, mean) here (.npy or .csv); needs --truth')
+    p.add_argument('--surface_percentile', type=float, default=95, help='the percentile of the percentile distance')
     return p
+
+
+def write_surface_scores(path, labels, table):
+    """table [n_volumes, 3, N] (hausdorff, percentile, mean) -> .npy (the table), or .csv (a header of label values, then
+    three rows per volume: hausdorff, percentile, mean)"""
+    if path.endswith('.npy'):
+        np.save(path, table)
+    elif path.endswith('.csv'):
+        with open(path, 'w') as f:
+            f.write(','.join(str(int(v)) for v in labels) + '\n')
+            for volume in table:
+                for row in volume:
+                    f.write(','.join(repr(float(v)) for v in row) + '\n')
+    else:
+        raise ValueError('--surface_scores takes a .npy or a .csv path, got %s' % path)
 
 
 def write_scores(path, labels, table):
@@ -62,6 +83,12 @@ def main(argv=None):
         parser.error('--scores needs --truth')
     if args.scores is not None and not args.scores.endswith(('.npy', '.csv')):
         parser.error('--scores takes a .npy or a .csv path')
+    if args.surface_scores is not None and args.truth is None:
+        parser.error('--surface_scores needs --truth')
+    if args.surface_scores is not None and not args.surface_scores.endswith(('.npy', '.csv')):
+        parser.error('--surface_scores takes a .npy or a .csv path')
+    if not 0 <= args.surface_percentile <= 100:
+        parser.error('--surface_percentile lies in 0 .. 100')
     from synthsr_amd import volumes as V
     from synthsr_amd.predict_segmentation import predict_segmentation, dice_scores, label_values, mean_dice
     labels = label_values(args.labels)
@@ -77,13 +104,23 @@ def main(argv=None):
     if len(truths) != len(outs):
         raise ValueError('%d ground-truth label maps for %d segmentations' % (len(truths), len(outs)))
     table = np.stack([dice_scores(o, t, labels) for o, t in zip(outs, truths)])
-    for o, row in zip(outs, table):
+    surface = None
+    if args.surface_scores is not None:
+        from synthsr_amd.predict_segmentation import surface_distances, mean_surface_scores, SURFACE_KEYS
+        per_volume = [surface_distances(o, t, labels, percentile=args.surface_percentile) for o, t in zip(outs, truths)]
+        surface = np.stack([np.stack([s[key] for key in SURFACE_KEYS]) for s in per_volume])
+    for i, (o, row) in enumerate(zip(outs, table)):
         print(o)
         for v, d in zip(labels, row):
             print('  label %5d  Dice %s' % (v, 'absent' if np.isnan(d) else '%.4f' % d))
         print('  mean Dice %.4f' % mean_dice(row))
+        if surface is not None:
+            print('  mean Hausdorff %.4f  mean HD%g %.4f  mean surface distance %.4f'
+                  % ((mean_surface_scores(per_volume[i])[0], args.surface_percentile) + mean_surface_scores(per_volume[i])[1:]))
     if args.scores is not None:
         write_scores(args.scores, labels, table)
+    if surface is not None:
+        write_surface_scores(args.surface_scores, labels, surface)
     return table
 
 

@@ -16,6 +16,7 @@ ARCH = 'gfx950'
 SOURCES = [('generator.hip', ['-ffp-contract=off']),
            ('unet_pointwise.hip', []),
            ('ssim.hip', []),
+           ('seg_surface.hip', []),
            ('critic.hip', []),
            ('conv_bf16.hip', []),
            ('conv_split.hip', []),

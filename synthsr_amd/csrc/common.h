@@ -271,6 +271,14 @@ __device__ __forceinline__ void syn_minmax_update(uint32_t* mm, float mn, float 
 #endif
 
 #ifdef __HIPCC__
+// head channel of a label value, or -1 (the softmax-head kernels of unet_pointwise.hip, seg_surface.hip)
+__device__ __forceinline__ int shd_class(int lab, const int32_t* __restrict__ lut, int lut_n, int N) {
+  const int k = (lab >= 0 && lab < lut_n) ? lut[lab] : -1;
+  return (k >= 0 && k < N) ? k : -1;
+}
+#endif
+
+#ifdef __HIPCC__
 // two fp32 values -> their three bf16 pieces (packed pairs, low half = first value): a = a0 + a1 + a2 exactly, every piece
 // rounded to nearest even from what the previous ones left (conv_split.hip; one v_cvt_pk_bf16_f32 + two subtractions each)
 __device__ __forceinline__ uint32_t syn_pack_bf16x2(float lo, float hi) {

@@ -1487,12 +1487,6 @@ static_assert(ShdFwdLds(24, 33, true, true).cls == ShdFwdLds(24, 33, true).cls &
               ShdBwdLds(4, 1, true).msk % 2 == 0 && (ShdBwdLds(64, 64, true).total * 4 + 8192 + 16) <= 65536,
               "LDS layout of the weighted softmax-head kernels");
 
-// head channel of a label value, or -1
-__device__ __forceinline__ int shd_class(int lab, const int32_t* __restrict__ lut, int lut_n, int N) {
-  const int k = (lab >= 0 && lab < lut_n) ? lut[lab] : -1;
-  return (k >= 0 && k < N) ? k : -1;
-}
-
 // The steps that the tile kernels share.  tid = 64 wave + lane, lane = 16 quad + col.
 // Head into LDS: wl [C][SW] (columns n >= N zero), BatchNorm scale / shift, bias; column(n) = the head column behind channel n.
 template <typename Column>

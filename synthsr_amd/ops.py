@@ -1001,6 +1001,47 @@ def seg_label_counts(a, b, lut, N, counts=None):
     return counts
 
 
+SURFACE_MAX_SIDE = 1024   # include/synthsr_hip.h: synthsr_seg_surface_dist2
+
+
+def seg_surface_workspace_bytes(shape, N):
+    """bytes of device scratch seg_surface_dist2 needs for label maps of `shape` and N head channels"""
+    if len(shape) != 3 or not all(1 <= int(s) <= SURFACE_MAX_SIDE for s in shape) or not 1 <= int(N) <= 64:
+        raise ValueError('seg_surface_dist2 takes label maps [d0, d1, d2] with sides 1 .. %d and 1 <= N <= 64 (got %s, N = %r)'
+                         % (SURFACE_MAX_SIDE, tuple(shape), N))
+    return int(_L().synthsr_seg_surface_workspace_bytes(_lib.i3(shape), int(N)))
+
+
+def seg_surface_dist2(a, b, lut, N, d2_ab=None, d2_ba=None, workspace=None):
+    """(d2_ab, d2_ba), int32 of the maps' shape, for two int32 label maps [d0, d1, d2] of equal shape: at a surface voxel of
+    class k of `a` (a face neighbour outside the volume or of another class) d2_ab holds the squared distance, in voxels, to the
+    nearest surface voxel of class k of `b` (INT32_MAX when b has none), elsewhere -1; d2_ba likewise with the maps exchanged.
+    lut (int32): label value -> channel or -1.  Exact integers.  workspace: a uint8 tensor of seg_surface_workspace_bytes()
+    (taken from torch when None)."""
+    if a.dtype != torch.int32 or b.dtype != torch.int32 or lut.dtype != torch.int32:
+        raise ValueError('seg_surface_dist2 takes the label maps and the lookup table as int32 (got %s, %s, %s)'
+                         % (a.dtype, b.dtype, lut.dtype))
+    if a.dim() != 3 or a.shape != b.shape or lut.numel() < 1:
+        raise ValueError('seg_surface_dist2: label maps of shapes %s and %s' % (tuple(a.shape), tuple(b.shape)))
+    N = int(N)
+    need = seg_surface_workspace_bytes(a.shape, N)
+    outs = []
+    for name, t in (('d2_ab', d2_ab), ('d2_ba', d2_ba)):
+        if t is None:
+            t = torch.empty(a.shape, dtype=torch.int32, device=a.device)
+        if t.numel() != a.numel() or t.dtype != torch.int32:
+            raise ValueError('seg_surface_dist2: %s should be int32 with one value per voxel' % name)
+        outs.append(t)
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.uint8, device=a.device)
+    if workspace.dtype != torch.uint8 or workspace.numel() < need or workspace.data_ptr() % 16:
+        raise ValueError('seg_surface_dist2: the workspace should be a 16-byte aligned uint8 tensor of at least %d bytes' % need)
+    _lib.check(_L().synthsr_seg_surface_dist2(_lib.ptr(a), _lib.ptr(b), _lib.i3(a.shape), _lib.ptr(lut), int(lut.numel()), N,
+                                              _lib.ptr(outs[0]), _lib.ptr(outs[1]), _lib.ptr(workspace), workspace.numel(),
+                                              _lib.stream()), 'seg_surface_dist2')
+    return outs[0], outs[1]
+
+
 def adam_step(p, g, m, v, lr_t, beta1=0.9, beta2=0.999, eps=1e-7, grad_scale=1.0):
     lib = _L()
     _lib.check(lib.synthsr_adam_step(_lib.ptr(p), _lib.ptr(g), _lib.ptr(m), _lib.ptr(v), p.numel(), float(lr_t),

@@ -244,3 +244,75 @@ def dice_scores(seg, truth, label_list, device=None):
     counts = ops.seg_label_counts(torch.from_numpy(a).to(dev).reshape(-1), torch.from_numpy(b).to(dev).reshape(-1),
                                   torch.from_numpy(lut).to(dev), int((lut >= 0).sum()))
     return dice_from_counts(counts.cpu().numpy())
+
+
+SURFACE_KEYS = ('hausdorff', 'hd_percentile', 'mean')
+
+
+def surface_scores_from_d2(cls_a, d2_ab, cls_b, d2_ba, N, percentile=95, voxel_size=1.0):
+    """The host half of surface_distances(): float64 scores per head channel from exact squared distances.
+
+    cls_a, d2_ab: arrays of equal shape, the head channel of each voxel of map a and its squared distance to the surface of the
+    same class in map b (ops.seg_surface_dist2: < 0 at voxels that are no surface voxels, which are left out, INT32_MAX when b
+    has no surface of the class); whole volumes or only the gathered surface voxels.  cls_b, d2_ba: the same for map b.
+    With D = voxel_size * sqrt of the distances of class k from both directions: hausdorff = max(D), hd_percentile =
+    numpy.percentile(D, percentile), mean = D.mean(); a class without a surface voxel in one of the maps (or both) scores NaN.
+    Returns a dict of float64 [N] arrays under SURFACE_KEYS and the int64 [N] surface voxel counts 'n_seg' (map a) and
+    'n_truth' (map b)."""
+    N = int(N)
+    if not 0 <= float(percentile) <= 100:
+        raise ValueError('percentile should lie in 0 .. 100, got %r' % (percentile,))
+    sides = []
+    for what, cls, d2 in (('a', cls_a, d2_ab), ('b', cls_b, d2_ba)):
+        cls, d2 = np.asarray(cls).reshape(-1), np.asarray(d2).reshape(-1)
+        if cls.shape != d2.shape:
+            raise ValueError('surface_scores_from_d2: %d classes for %d distances of map %s' % (cls.size, d2.size, what))
+        keep = d2 >= 0
+        cls, d2 = cls[keep].astype(np.int64), d2[keep].astype(np.int64)
+        if cls.size and (cls.min() < 0 or cls.max() >= N):
+            raise ValueError('surface_scores_from_d2: a surface voxel of map %s has no class in 0 .. %d' % (what, N - 1))
+        order = np.argsort(cls, kind='stable')
+        counts = np.bincount(cls, minlength=N).astype(np.int64)
+        sides.append((d2[order], np.concatenate([[0], np.cumsum(counts)]), counts))
+    out = {key: np.full(N, np.nan, dtype=np.float64) for key in SURFACE_KEYS}
+    far = np.iinfo(np.int32).max
+    for k in range(N):
+        parts = [d2[start[k]:start[k + 1]] for d2, start, _ in sides]
+        if parts[0].size == 0 or parts[1].size == 0:
+            continue
+        d2 = np.concatenate(parts)
+        if d2.max() >= far:     # the other map has no surface of the class: cannot happen with both present
+            continue
+        D = np.sqrt(d2.astype(np.float64)) * float(voxel_size)
+        out['hausdorff'][k] = D.max()
+        out['hd_percentile'][k] = np.percentile(D, percentile)
+        out['mean'][k] = D.mean()
+    out['n_seg'], out['n_truth'] = sides[0][2], sides[1][2]
+    return out
+
+
+def mean_surface_scores(scores):
+    """the three means over the labels present in both maps (NaN when there is none), in the order of SURFACE_KEYS"""
+    return tuple(mean_dice(scores[key]) for key in SURFACE_KEYS)
+
+
+def surface_distances(seg, truth, label_list, percentile=95, voxel_size=1.0, device=None):
+    """Hausdorff distance, `percentile`-th percentile distance and mean distance between the surfaces of two label maps of equal
+    shape (arrays or paths), per label in the order of `label_list`, in units of `voxel_size`: surface_scores_from_d2 of the
+    exact squared distance maps of ops.seg_surface_dist2.  Only the surface voxels leave the device."""
+    import torch
+    from . import ops
+    lut = segmentation_lut(label_list)
+    a, b = _label_map(seg), _label_map(truth)
+    if a.ndim != 3 or a.shape != b.shape:
+        raise ValueError('surface_distances: 3-D label maps of equal shape, got %s and %s' % (a.shape, b.shape))
+    dev = device or 'cuda'
+    N = int((lut >= 0).sum())
+    lut_d = torch.from_numpy(lut).to(dev)
+    a_d, b_d = torch.from_numpy(a).to(dev), torch.from_numpy(b).to(dev)
+    d2_ab, d2_ba = ops.seg_surface_dist2(a_d, b_d, lut_d, N)
+    sides = []
+    for m, d2 in ((a_d, d2_ab), (b_d, d2_ba)):
+        at = d2 >= 0                      # surface voxels: their label values are inside the table
+        sides += [lut_d[m[at].long()].cpu().numpy(), d2[at].cpu().numpy()]
+    return surface_scores_from_d2(*sides, N=N, percentile=percentile, voxel_size=voxel_size)
