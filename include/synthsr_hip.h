@@ -690,6 +690,29 @@ int synthsr_seg_surface_dist2(const int32_t* a, const int32_t* b, const int* sha
                               int32_t* d2_ab, int32_t* d2_ba, void* workspace, int64_t workspace_bytes,
                               synthsr_stream_t stream);
 
+/* --- connected components of a label map; the largest component per group -----------------------------------------------
+ * labels [shape[0]][shape[1]][shape[2]] label map; lut [lut_n] maps a label value to a GROUP 0 .. G-1 or to -1 (values < 0,
+ * >= lut_n or mapped outside 0 .. G-1: in no group).  Two voxels are connected when they are in the same group and adjacent
+ * under `connectivity`: 6 (faces), 18 (faces and edges) or 26 (faces, edges and corners); voxels of different groups never
+ * join.  components: comp [nvox] int32, every element written: the smallest linear index (x fastest) of any voxel of v's
+ *   component, -1 for a voxel in no group.  The result is unique, hence the same bits for every launch order; three launches
+ *   whatever the map, and no workgroup waits on another.
+ * keep_largest: comp as written by components for the same labels, lut and G.  Per group the component with the most voxels is
+ *   kept, of several of that size the one with the smallest root.  out [nvox]: fill_value at every voxel whose component is not
+ *   the one kept for its group, labels[v] at every other voxel (voxels in no group included); fill_value is written as is,
+ *   whatever group it is in.  out may be labels.  stats [G][4] int64: the root of the kept component (-1: the group is empty),
+ *   its size, the number of components of the group, the number of voxels of the group.  Four launches.
+ * Limits: every side 1 .. 1024, 1 <= G <= 64.  workspace: synthsr_seg_components_workspace_bytes(shape) bytes of device
+ * memory for either call, 16-byte aligned, owned by the caller (the library allocates nothing); its contents need no
+ * initialisation and mean nothing afterwards.  A NULL pointer, a side or G outside the limits, lut_n < 1, another
+ * connectivity, a misaligned or too small workspace return SYNTHSR_EINVAL before any launch (workspace_bytes: -1). */
+int64_t synthsr_seg_components_workspace_bytes(const int* shape);
+int synthsr_seg_components(const int32_t* labels, const int* shape, const int32_t* lut, int lut_n, int G, int connectivity,
+                           int32_t* comp, void* workspace, int64_t workspace_bytes, synthsr_stream_t stream);
+int synthsr_seg_keep_largest(const int32_t* labels, const int32_t* comp, const int* shape, const int32_t* lut, int lut_n, int G,
+                             int32_t fill_value, int32_t* out, int64_t* stats, void* workspace, int64_t workspace_bytes,
+                             synthsr_stream_t stream);
+
 /* --- a frozen or inference softmax-headed U-Net in bf16 ------------------------------------------------------------------
  * The feature map x [nvox][C] is bf16 (8-byte aligned: one channel quad per vector load); BatchNorm statistics, gamma / beta,
  * the head's fp32 master weights w / b, posteriors, prev and the Dice sums stay fp32, so the arithmetic on a given bf16 x is

@@ -6,6 +6,8 @@ the result with the per-label Dice coefficient and the distances between the sur
                                            [--lr_pairs P.npy] [--posteriors <path>] [--disable_flipping]
                                            [--n_levels 5 --conv_per_level 2 --unet_feat 24 --feat_mult 2 --activation elu]
                                            [--dtype f32|bf16]
+                                           [--keep_largest per_label|foreground|G.npy [--connectivity 6|18|26] [--fill_label V]]
+                                           [--volumes V.npy|V.csv]
                                            [--truth <path> [--scores S.npy|S.csv]
                                                             [--surface_scores D.npy|D.csv [--surface_percentile 95]]]
 
@@ -14,7 +16,11 @@ into a folder carry the suffix _seg.  --labels: the label values in head-channel
 segmentation_label_list); --lr_pairs: a [K, 2] array of (left value, right value) pairs whose channels are swapped in the
 flipped pass of the test-time augmentation.  --surface_scores: per label the Hausdorff distance, the --surface_percentile-th
 percentile distance and the mean distance between the surfaces of segmentation and ground truth, in mm (label maps are written
-at 1 mm): .npy [n_volumes, 3, N] in that order; .csv a header of label values, then three rows per volume in that order."""
+at 1 mm): .npy [n_volumes, 3, N] in that order; .csv a header of label values, then three rows per volume in that order.
+--keep_largest: write only the largest connected component of every group of labels (per_label: every label but the fill label
+is a group; foreground: they form one group; G.npy: a group id per head channel, -1 = untouched), under --connectivity; the
+removed voxels become --fill_label (default: the first label of --labels).  Dice and surface scores are then those of the
+filtered maps.  --volumes: the volume of every label in every written map, in mm^3: .npy [n_volumes, N]; .csv as --scores."""
 import os
 import sys
 from argparse import ArgumentParser
@@ -40,6 +46,13 @@ def build_parser():
     p.add_argument('--activation', type=str, default='elu')
     p.add_argument('--dtype', choices=('f32', 'bf16'), default='f32',
                    help='arithmetic of the network: bf16 = bf16 activations and packed weights, fp32 head and posteriors')
+    p.add_argument('--keep_largest', default=None,
+                   help='keep the largest connected component per group: per_label, foreground, or a .npy of group ids per label')
+    p.add_argument('--connectivity', type=int, choices=(6, 18, 26), default=6,
+                   help='voxels are connected through faces (6), faces and edges (18) or faces, edges and corners (26)')
+    p.add_argument('--fill_label', type=int, default=None,
+                   help='the label value removed voxels take (default: the first label of --labels)')
+    p.add_argument('--volumes', default=None, help='write the per-label volumes in mm^3 here (.npy or .csv)')
     p.add_argument('--truth', default=None, help='ground-truth label map (or folder, sorted like the images): score with Dice')
     p.add_argument('--scores', default=None, help='write the per-label Dice table here (.npy or .csv); needs --truth')
     p.add_argument('--surface_scores', default=None,
@@ -63,7 +76,7 @@ def write_surface_scores(path, labels, table):
         raise ValueError('--surface_scores takes a .npy or a .csv path, got %s' % path)
 
 
-def write_scores(path, labels, table):
+def write_scores(path, labels, table, flag='--scores'):
     """table [n_volumes, N] -> .npy (the table), or .csv (a header of label values, one row per volume)"""
     if path.endswith('.npy'):
         np.save(path, table)
@@ -73,7 +86,12 @@ def write_scores(path, labels, table):
             for row in table:
                 f.write(','.join(repr(float(v)) for v in row) + '\n')
     else:
-        raise ValueError('--scores takes a .npy or a .csv path, got %s' % path)
+        raise ValueError('%s takes a .npy or a .csv path, got %s' % (flag, path))
+
+
+def write_volumes(path, labels, table):
+    """table [n_volumes, N] of volumes in mm^3 -> the layout of write_scores"""
+    write_scores(path, labels, table, flag='--volumes')
 
 
 def main(argv=None):
@@ -89,6 +107,13 @@ def main(argv=None):
         parser.error('--surface_scores takes a .npy or a .csv path')
     if not 0 <= args.surface_percentile <= 100:
         parser.error('--surface_percentile lies in 0 .. 100')
+    if args.volumes is not None and not args.volumes.endswith(('.npy', '.csv')):
+        parser.error('--volumes takes a .npy or a .csv path')
+    keep_largest = args.keep_largest
+    if keep_largest is not None and keep_largest not in ('per_label', 'foreground'):
+        if not keep_largest.endswith('.npy'):
+            parser.error('--keep_largest takes per_label, foreground or a .npy path')
+        keep_largest = np.load(keep_largest)
     from synthsr_amd import volumes as V
     from synthsr_amd.predict_segmentation import predict_segmentation, dice_scores, label_values, mean_dice
     labels = label_values(args.labels)
@@ -97,7 +122,11 @@ def main(argv=None):
                                 path_posteriors=args.posteriors, lr_pairs=lr_pairs, disable_flipping=args.disable_flipping,
                                 n_levels=args.n_levels, nb_conv_per_level=args.nb_conv_per_level,
                                 unet_feat_count=args.unet_feat_count, feat_multiplier=args.feat_multiplier,
-                                activation=args.activation, dtype=args.dtype)
+                                activation=args.activation, dtype=args.dtype, keep_largest=keep_largest,
+                                connectivity=args.connectivity, fill_label=args.fill_label)
+    if args.volumes is not None:
+        from synthsr_amd.predict_segmentation import label_volumes
+        write_volumes(args.volumes, labels, np.stack([label_volumes(o, labels) for o in outs]))   # written at 1 mm
     if args.truth is None:
         return None
     truths = V.list_images_in_folder(os.path.abspath(args.truth))

@@ -17,6 +17,7 @@ SOURCES = [('generator.hip', ['-ffp-contract=off']),
            ('unet_pointwise.hip', []),
            ('ssim.hip', []),
            ('seg_surface.hip', []),
+           ('seg_components.hip', []),
            ('critic.hip', []),
            ('conv_bf16.hip', []),
            ('conv_split.hip', []),
@@ -39,8 +40,8 @@ def _newer(src_list, target):
 
 def build(force=False, verbose=True):
     hipcc = _hipcc()
-    deps = [os.path.join(CSRC, 'common.h'), os.path.join(os.path.dirname(HERE), 'include', 'synthsr_hip.h'),
-            os.path.abspath(__file__)]
+    deps = [os.path.join(CSRC, 'common.h'), os.path.join(CSRC, 'seg_components_uf.h'),
+            os.path.join(os.path.dirname(HERE), 'include', 'synthsr_hip.h'), os.path.abspath(__file__)]
     objs = []
     procs = []
     for name, extra in SOURCES:

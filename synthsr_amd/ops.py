@@ -1042,6 +1042,77 @@ def seg_surface_dist2(a, b, lut, N, d2_ab=None, d2_ba=None, workspace=None):
     return outs[0], outs[1]
 
 
+COMPONENTS_MAX_GROUPS = 64   # include/synthsr_hip.h: synthsr_seg_components
+CONNECTIVITIES = (6, 18, 26)
+
+
+def seg_components_workspace_bytes(shape):
+    """bytes of device scratch seg_components and seg_keep_largest need for a label map of `shape`"""
+    if len(shape) != 3 or not all(1 <= int(s) <= SURFACE_MAX_SIDE for s in shape):
+        raise ValueError('seg_components takes a label map [d0, d1, d2] with sides 1 .. %d (got %s)'
+                         % (SURFACE_MAX_SIDE, tuple(shape)))
+    return int(_L().synthsr_seg_components_workspace_bytes(_lib.i3(shape)))
+
+
+def _seg_components_args(what, labels, lut, G, workspace):
+    if labels.dtype != torch.int32 or lut.dtype != torch.int32:
+        raise ValueError('%s takes the label map and the lookup table as int32 (got %s, %s)' % (what, labels.dtype, lut.dtype))
+    if labels.dim() != 3 or lut.numel() < 1:
+        raise ValueError('%s: a label map [d0, d1, d2] and a lookup table of at least one entry, got shapes %s and %s'
+                         % (what, tuple(labels.shape), tuple(lut.shape)))
+    need = seg_components_workspace_bytes(labels.shape)
+    if not 1 <= int(G) <= COMPONENTS_MAX_GROUPS:
+        raise ValueError('%s: 1 <= G <= %d groups (got %r)' % (what, COMPONENTS_MAX_GROUPS, G))
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.uint8, device=labels.device)
+    if workspace.dtype != torch.uint8 or workspace.numel() < need or workspace.data_ptr() % 16:
+        raise ValueError('%s: the workspace should be a 16-byte aligned uint8 tensor of at least %d bytes' % (what, need))
+    return workspace
+
+
+def seg_components(labels, lut, G, connectivity=6, comp=None, workspace=None):
+    """comp, int32 of the map's shape, for an int32 label map [d0, d1, d2]: the smallest linear index of any voxel of the voxel's
+    connected component, -1 for a voxel in no group.  lut (int32): label value -> group 0 .. G-1 or -1; voxels are connected
+    when they are in the same group and adjacent under `connectivity` (6: faces, 18: and edges, 26: and corners).  Exact and
+    unique.  workspace: a uint8 tensor of seg_components_workspace_bytes() (taken from torch when None)."""
+    workspace = _seg_components_args('seg_components', labels, lut, G, workspace)
+    if connectivity not in CONNECTIVITIES:
+        raise ValueError('seg_components: connectivity is 6, 18 or 26 (got %r)' % (connectivity,))
+    if comp is None:
+        comp = torch.empty(labels.shape, dtype=torch.int32, device=labels.device)
+    if comp.numel() != labels.numel() or comp.dtype != torch.int32:
+        raise ValueError('seg_components: comp should be int32 with one value per voxel')
+    _lib.check(_L().synthsr_seg_components(_lib.ptr(labels), _lib.i3(labels.shape), _lib.ptr(lut), int(lut.numel()), int(G),
+                                           int(connectivity), _lib.ptr(comp), _lib.ptr(workspace), workspace.numel(),
+                                           _lib.stream()), 'seg_components')
+    return comp
+
+
+def seg_keep_largest(labels, comp, lut, G, fill_value, out=None, stats=None, workspace=None):
+    """(out, stats) for an int32 label map and its component map (seg_components with the same lut and G): out holds fill_value
+    at every voxel whose component is not the largest of its group (of several of that size: the one with the smallest root),
+    the label value elsewhere, voxels in no group included; out may be `labels`.  stats, int64 [G, 4]: root of the kept
+    component (-1: empty group), its size, the components and the voxels of the group."""
+    workspace = _seg_components_args('seg_keep_largest', labels, lut, G, workspace)
+    G = int(G)
+    if comp.dtype != torch.int32 or comp.numel() != labels.numel():
+        raise ValueError('seg_keep_largest: comp should be int32 with one value per voxel')
+    if not -2 ** 31 <= int(fill_value) < 2 ** 31:
+        raise ValueError('seg_keep_largest: fill_value should fit int32 (got %r)' % (fill_value,))
+    if out is None:
+        out = torch.empty(labels.shape, dtype=torch.int32, device=labels.device)
+    if out.numel() != labels.numel() or out.dtype != torch.int32:
+        raise ValueError('seg_keep_largest: out should be int32 with one value per voxel')
+    if stats is None:
+        stats = torch.empty(G, 4, dtype=torch.int64, device=labels.device)
+    if stats.numel() != 4 * G or stats.dtype != torch.int64:
+        raise ValueError('seg_keep_largest: stats should be int64 [%d, 4]' % G)
+    _lib.check(_L().synthsr_seg_keep_largest(_lib.ptr(labels), _lib.ptr(comp), _lib.i3(labels.shape), _lib.ptr(lut),
+                                             int(lut.numel()), G, int(fill_value), _lib.ptr(out), _lib.ptr(stats),
+                                             _lib.ptr(workspace), workspace.numel(), _lib.stream()), 'seg_keep_largest')
+    return out, stats
+
+
 def adam_step(p, g, m, v, lr_t, beta1=0.9, beta2=0.999, eps=1e-7, grad_scale=1.0):
     lib = _L()
     _lib.check(lib.synthsr_adam_step(_lib.ptr(p), _lib.ptr(g), _lib.ptr(m), _lib.ptr(v), p.numel(), float(lr_t),

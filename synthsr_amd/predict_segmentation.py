@@ -9,6 +9,9 @@ With flip averaging the first pass keeps its posteriors (UNet3D.predict_probs); 
 its first (left-right) axis, averages them with its own mirrored ones -- channels of left and right structures swapped --
 inside the head kernel and writes the label map of the average.  Without it no posterior is ever formed.
 
+Asked to (keep_largest), the label map is cleaned on the device before it is written: of every group of labels only the
+largest connected component stays (ops.seg_components, ops.seg_keep_largest), the rest takes the fill label.
+
 The head's channel order is `segmentation_label_list`, as in training_segmentation().  fp32 only."""
 import os
 import numpy as np
@@ -73,6 +76,63 @@ def mean_dice(scores):
     return float(scores[present].mean()) if present.any() else float('nan')
 
 
+GROUPINGS = ('per_label', 'foreground')
+MAX_GROUPS = 64   # include/synthsr_hip.h: synthsr_seg_components
+
+
+def component_groups(label_list, groups='per_label', fill_label=None):
+    """(lut, G, fill_value) for connected_components / keep_largest_components: lut, int32, maps a label value to its group
+    0 .. G-1 or to -1 (left untouched); fill_value is what removed voxels become: `fill_label`, by default the first listed
+    label (conventionally background).  groups:
+      'per_label'   every listed label except the fill label is a group of its own, in the order of the list
+      'foreground'  all listed labels except the fill label form one group
+      int array [N] the group of every head channel, -1: left untouched (SynthSeg's topology classes); the ids used are
+                    0 .. G-1 without gaps.  The fill label is not treated specially here.
+    At most 64 groups."""
+    labels = label_values(label_list)
+    if fill_label is None:
+        fill_value = int(labels[0])
+    else:
+        if fill_label != np.round(fill_label) or not -2 ** 31 <= int(fill_label) < 2 ** 31:
+            raise ValueError('fill_label should be an integer label value, got %r' % (fill_label,))
+        fill_value = int(fill_label)
+    if isinstance(groups, str):
+        if groups not in GROUPINGS:
+            raise ValueError("groups should be 'per_label', 'foreground' or an array of group ids per label, got %r" % (groups,))
+        ids = np.full(len(labels), -1, dtype=np.int64)
+        others = labels != fill_value
+        ids[others] = np.arange(int(others.sum())) if groups == 'per_label' else 0
+    else:
+        ids = np.asarray(hm.load_array_if_path(groups))
+        if ids.ndim != 1 or ids.size != len(labels):
+            raise ValueError('groups should hold one group id per listed label (%d), got an array of shape %s'
+                             % (len(labels), ids.shape))
+        if np.any(ids != np.round(ids)) or np.any(ids < -1):
+            raise ValueError('groups should hold integer group ids, -1 for a label that is left untouched')
+        ids = ids.astype(np.int64)
+    used = np.unique(ids[ids >= 0])
+    G = len(used)
+    if G < 1:
+        raise ValueError('the grouping leaves no label in any group')
+    if G > MAX_GROUPS:
+        raise ValueError('%d groups: connected components take at most %d groups' % (G, MAX_GROUPS))
+    if not np.array_equal(used, np.arange(G)):
+        raise ValueError('group ids should be 0 .. %d without gaps, got %s' % (G - 1, used.tolist()))
+    lut = np.full(int(labels.max()) + 1, -1, dtype=np.int32)
+    lut[labels] = ids.astype(np.int32)
+    return lut, G, fill_value
+
+
+def _filter_on_device(seg, lut, G, fill_value, connectivity):
+    """(out, stats) on the device for a contiguous int32 device label map [d0, d1, d2]"""
+    import torch
+    from . import ops
+    lut_d = torch.from_numpy(lut).to(seg.device)
+    workspace = torch.empty(ops.seg_components_workspace_bytes(seg.shape), dtype=torch.uint8, device=seg.device)
+    comp = ops.seg_components(seg, lut_d, G, connectivity, workspace=workspace)
+    return ops.seg_keep_largest(seg, comp, lut_d, G, fill_value, workspace=workspace)
+
+
 def check_head_width(state, table, labels):
     """the weight file's head should have one channel per listed label"""
     name = table.head['w']
@@ -130,13 +190,22 @@ class SegmentationPredictor:
             self.nets[key] = net
         return self.nets[key]
 
-    def segment_volume(self, S, flipping=True, lr_pairs=None, return_posteriors=False):
+    def segment_volume(self, S, flipping=True, lr_pairs=None, return_posteriors=False, keep_largest=None, connectivity=6,
+                       fill_label=None, crop=None):
         """S [W0,W1,W2] (numpy, padded: every side a multiple of 2**(n_levels-1)) -> int32 label map [W0,W1,W2] of label
         values (numpy); with return_posteriors also the posteriors [W0,W1,W2,N] float32 the map is the argmax of.
         flipping: average with the pass on the volume flipped along the first (left-right) axis, the channels of each
-        (left value, right value) pair of lr_pairs swapped."""
+        (left value, right value) pair of lr_pairs swapped.
+        crop: three slices; what is returned is cut to them, on the device.
+        keep_largest: None, or a grouping of component_groups() ('per_label', 'foreground', group ids per channel): the
+        returned (cropped) map keeps only the largest connected component of every group under `connectivity` (6, 18, 26), the
+        other voxels of the group become `fill_label` (default: the first listed label).  The filter runs on the device.  The
+        posteriors are returned unchanged: they are those of the unfiltered map."""
         import torch
         perm = lr_permutation(self.labels, lr_pairs)
+        grouping = None if keep_largest is None else component_groups(self.labels, keep_largest, fill_label)
+        if connectivity not in (6, 18, 26):
+            raise ValueError('connectivity is 6, 18 or 26, got %r' % (connectivity,))
         S = np.asarray(S)
         if S.ndim != 3:
             raise ValueError('segment_volume takes one 3-D volume, got an array of shape %s' % (S.shape,))
@@ -157,9 +226,15 @@ class SegmentationPredictor:
             out = self._labels_dev[torch.argmax(probs, dim=1)]
         else:
             out = net.predict_labels(x, self._labels_dev)
-        seg = out.reshape(S.shape).cpu().numpy().astype(np.int32, copy=False)
+        out = out.reshape(S.shape)
+        if crop is not None:
+            out = out[tuple(crop)]
+        if grouping is not None:
+            out = _filter_on_device(out.to(torch.int32).contiguous(), grouping[0], grouping[1], grouping[2], connectivity)[0]
+        seg = out.cpu().numpy().astype(np.int32, copy=False)
         if return_posteriors:
-            return seg, probs.reshape(*S.shape, N).cpu().numpy()
+            probs = probs.reshape(*S.shape, N)
+            return seg, (probs if crop is None else probs[tuple(crop)]).cpu().numpy()
         return seg
 
 
@@ -172,12 +247,17 @@ def _suffixed(path, suffix):
 
 def predict_segmentation(path_images, path_segmentations, path_model, segmentation_label_list, path_posteriors=None,
                          lr_pairs=None, disable_flipping=False, n_levels=5, nb_conv_per_level=2, unet_feat_count=24,
-                         feat_multiplier=2, activation='elu', device=None, verbose=True, predictor=None, dtype='f32'):
+                         feat_multiplier=2, activation='elu', device=None, verbose=True, predictor=None, dtype='f32',
+                         keep_largest=None, connectivity=6, fill_label=None):
     """The file / folder contract of predict.predict(): `path_images` / `path_segmentations` (and `path_posteriors`, if
     given) are all single files (.nii, .nii.gz, .mgz, .npz) or all folders; in folders the outputs carry the suffixes
     `_seg` and `_posteriors`.  Label maps are saved as int32 in the 1 mm RAS frame predict() writes in.  Returns the paths
     of the label maps.  dtype: 'f32' or 'bf16', the arithmetic of the network (SegmentationPredictor); posteriors are
-    written as float32 either way."""
+    written as float32 either way.
+    keep_largest: None (the raw argmax), or a grouping of component_groups(): the label map that is written keeps only the largest
+    connected component of every group under `connectivity`, the other voxels of the group become `fill_label` (default: the first
+    listed label).  The filter runs on the device on the cropped map, so the file equals keep_largest_components() of the file
+    written without it.  Posteriors, when asked for, are written unchanged."""
     if dtype not in ('f32', 'bf16'):
         raise ValueError("dtype should be 'f32' or 'bf16', got %r" % (dtype,))
     if 32 % (2 ** (int(n_levels) - 1)) != 0:
@@ -214,11 +294,12 @@ def predict_segmentation(path_images, path_segmentations, path_model, segmentati
         S, idx, shape, aff2 = prepare_volume(im, aff)
         crop = tuple(slice(int(o), int(o) + int(n)) for o, n in zip(idx, shape))
         res = predictor.segment_volume(S, flipping=not disable_flipping, lr_pairs=lr_pairs,
-                                       return_posteriors=ppost is not None)
+                                       return_posteriors=ppost is not None, keep_largest=keep_largest,
+                                       connectivity=connectivity, fill_label=fill_label, crop=crop)
         seg = res[0] if ppost is not None else res
-        V.save_volume(np.ascontiguousarray(seg[crop]), aff2, None, pout, dtype='int32')
+        V.save_volume(np.ascontiguousarray(seg), aff2, None, pout, dtype='int32')
         if ppost is not None:
-            V.save_volume(np.ascontiguousarray(res[1][crop]), aff2, None, ppost, dtype='float32', n_dims=3)
+            V.save_volume(np.ascontiguousarray(res[1]), aff2, None, ppost, dtype='float32', n_dims=3)
     return outs
 
 
@@ -244,6 +325,48 @@ def dice_scores(seg, truth, label_list, device=None):
     counts = ops.seg_label_counts(torch.from_numpy(a).to(dev).reshape(-1), torch.from_numpy(b).to(dev).reshape(-1),
                                   torch.from_numpy(lut).to(dev), int((lut >= 0).sum()))
     return dice_from_counts(counts.cpu().numpy())
+
+
+def label_volumes(seg, label_list, voxel_volume=1.0):
+    """per-label volumes (float64 [N], in the order of `label_list`, background included) of a label map given as an array or
+    a path: voxel_volume times the voxels of each label, counted on the GPU (ops.seg_label_counts of the map against itself)"""
+    import torch
+    from . import ops
+    lut = segmentation_lut(label_list)
+    a = torch.from_numpy(_label_map(seg)).to('cuda').reshape(-1)
+    counts = ops.seg_label_counts(a, a, torch.from_numpy(lut).to('cuda'), int((lut >= 0).sum()))
+    return counts[1].cpu().numpy().astype(np.float64) * float(voxel_volume)
+
+
+def connected_components(label_map, label_list, groups='per_label', connectivity=6, device=None):
+    """the component map of a 3-D label map (an array or a path) as int32 numpy: at every voxel the smallest linear index (C
+    order) of any voxel of its connected component, -1 at voxels in no group.  groups: component_groups(); connectivity: 6
+    (faces), 18 (faces and edges) or 26 (faces, edges and corners).  Labelled on the GPU (ops.seg_components)."""
+    import torch
+    from . import ops
+    lut, G, _ = component_groups(label_list, groups)
+    m = _label_map(label_map)
+    if m.ndim != 3:
+        raise ValueError('connected_components takes a 3-D label map, got shape %s' % (m.shape,))
+    dev = device or 'cuda'
+    return ops.seg_components(torch.from_numpy(m).to(dev), torch.from_numpy(lut).to(dev), G, connectivity).cpu().numpy()
+
+
+def keep_largest_components(seg, label_list, groups='per_label', connectivity=6, fill_label=None, device=None,
+                            return_stats=False):
+    """the 3-D label map `seg` (an array or a path) with only the largest connected component of every group kept (of several
+    of that size: the one that holds the smallest linear index); the other voxels of the group become `fill_label` (default: the
+    first listed label), voxels in no group stay.  int32 numpy; with return_stats also int64 [G, 4]: per group the root of the
+    kept component (-1: empty group), its size, the components and the voxels of the group.  Runs on the GPU."""
+    import torch
+    lut, G, fill_value = component_groups(label_list, groups, fill_label)
+    m = _label_map(seg)
+    if m.ndim != 3:
+        raise ValueError('keep_largest_components takes a 3-D label map, got shape %s' % (m.shape,))
+    out, stats = _filter_on_device(torch.from_numpy(m).to(device or 'cuda'), lut, G, fill_value, connectivity)
+    if return_stats:
+        return out.cpu().numpy(), stats.cpu().numpy()
+    return out.cpu().numpy()
 
 
 SURFACE_KEYS = ('hausdorff', 'hd_percentile', 'mean')
