@@ -410,6 +410,322 @@ __host__ __device__ inline uint32_t up_tapmask(int p, bool flipped) {
   return m;
 }
 
+// ---------------------------------------------------------------- pieces shared by the kernels below
+// XCD-aware tile order: workgroup b runs on XCD b%8 (observed dispatch order, speed only); every XCD gets a contiguous range
+// of tiles so that neighbouring tiles (shared halos) hit the same L2.  One tile per workgroup, bijective for any grid:
+__device__ __forceinline__ int xcd_tile_pos() {
+  const int nwg = gridDim.x, b = blockIdx.x;
+  const int q = nwg >> 3, r = nwg & 7, xcd = b & 7, j = b >> 3;
+  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + j;
+}
+// ... and the persistent kernels, whose gridDim.x is a multiple of 8: in every round of gridDim.x tiles, workgroup b (XCD b%8)
+// takes position (b%8)*(G/8) + b/8, so each XCD's L2 serves a contiguous run of neighbouring tiles.
+__device__ __forceinline__ int xcd_start_pos() {
+  const int G = gridDim.x;
+  return (blockIdx.x & 7) * (G >> 3) + (blockIdx.x >> 3);
+}
+// first voxel of tile t of a (tiles0, tiles1, tiles2) grid of T0 x T1 x T2 tiles, x fastest
+template <int T1, int T0 = FT0, int T2 = FT2>
+__device__ __forceinline__ void tile_origin(int t, int tiles1, int tiles2, int& z0, int& y0, int& x0) {
+  const int t2 = t % tiles2, t1 = (t / tiles2) % tiles1, t0 = t / (tiles2 * tiles1);
+  z0 = t0 * T0;
+  y0 = t1 * T1;
+  x0 = t2 * T2;
+}
+// halo-tile offset (in floats) of tap t of the 3x3x3 stencil in a [.][HY][HX][CKP] tile
+template <int HY, int HX, int CKP>
+__host__ __device__ constexpr int tap_halo_off(int t) { return (((t / 9) * HY + (t / 3) % 3) * HX + t % 3) * CKP; }
+
+__device__ __forceinline__ float4 as_f4(u32x4 v) {
+  return make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w));
+}
+// B fragment idx = g*NT + n of the 16x16x4 layout: voffset = lane*8, soffset = scalar (chunk, tap); immediates stay below 4096
+__device__ __forceinline__ float2 bload(__amdgpu_buffer_rsrc_t rw, int lane, int soff, int idx) {
+  const int hi = idx >> 2, lo = idx & 3;
+  const u32x2 v = __builtin_amdgcn_raw_buffer_load_b64(rw, lane * 8 + lo * 512, soff + hi * 2048, 0);
+  return make_float2(__uint_as_float(v.x), __uint_as_float(v.y));
+}
+// register r of a channel octet of the 4x4x1 layout
+__device__ __forceinline__ float wload(__amdgpu_buffer_rsrc_t rw, int lane, int soff, int r) {
+  return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rw, lane * 4 + r * 256, soff, 0));
+}
+
+// ---- VALU-lean halo staging.  On CDNA4 every vector-ALU instruction takes ~3-4 cycles out of the SIMD's MFMA issue
+// (tools/ubench/mfma_issue.hip), so the per-item address arithmetic is moved to the scalar unit: in every z-plane of the
+// FH0 x FH1 x FH2 halo tile ([voxel][CK + 4 pad] in LDS), thread t owns the same <= NJ (y, x, channel-quad) columns
+// j = t + 256 i of the plane's float4.  Their byte offsets relative to the tile origin and their LDS addresses are computed
+// ONCE per kernel; per item only `offset + scalar` and a bit-mask validity test remain.  The loads are raw buffer loads:
+// soffset carries the z-plane (scalar), out-of-volume elements get an offset beyond num_records and come back as zeros
+// (hardware range check) -- no per-element clamping or selects.  The launchers guarantee tensor bytes < 2^31.
+// Every member is force-inlined and the arrays are indexed by constants after unrolling, so `bad`, `yx` and the plane offsets
+// stay in scalar registers and the column tables in vector registers, as when this was written out in each kernel.
+//
+// HaloStagerWalk: persistent kernels that walk many tiles per workgroup (256 threads, 6 x FH1 x 18 halo).
+template <int FH1, int CK>
+struct HaloStagerWalk {
+  static constexpr int CKP = CK + 4, C4 = CK / 4;
+  static constexpr int PLANE4 = FH1 * FH2 * C4;       // 648 float4 per halo z-plane (FH1 = 6, CK = 24)
+  static constexpr int NJ = (PLANE4 + 255) / 256;     // 3 columns per thread
+  static constexpr int NLD = NJ * FH0;                // 18 halo loads per item
+  static constexpr uint32_t OOB = 0x80000000u;        // > num_records
+  __amdgpu_buffer_rsrc_t rin;
+  int rel[NJ], ldsa[NJ];
+  uint32_t cmask[NJ];  // one-hot (1 << hy) | (1 << (8 + hx)); all ones for j >= PLANE4
+  int plane_bytes, D0, D1, D2, Cin, tid;
+
+  __device__ __forceinline__ HaloStagerWalk(const float* in, int D0_, int D1_, int D2_, int Cin_, int tid_)
+      : D0(D0_), D1(D1_), D2(D2_), Cin(Cin_), tid(tid_) {
+    rin = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(in), 0, (int)((int64_t)D0 * D1 * D2 * Cin * 4), 0x00020000);
+#pragma unroll
+    for (int i = 0; i < NJ; ++i) {
+      const int j = tid + 256 * i;
+      const int hy = j / (FH2 * C4), r = j - hy * (FH2 * C4), hx = r / C4, c4 = r - hx * C4;
+      rel[i] = ((hy * D2 + hx) * Cin + c4 * 4) * 4;
+      ldsa[i] = ((hy * FH2 + hx) * CKP + c4 * 4);
+      cmask[i] = j < PLANE4 ? ((1u << hy) | (1u << (8 + hx))) : 0xFFFFFFFFu;
+    }
+    plane_bytes = D1 * D2 * Cin * 4;
+  }
+  // halo of channel chunk cc of the tile at (z0, y0, x0) -> staging registers, stg[plane * NJ + i]
+  __device__ __forceinline__ void load_all(int z0, int y0, int x0, int cc, float4 (&stg)[NLD]) const {
+    // invalid local rows/columns of this tile (scalar): hy valid iff 0 <= y0-1+hy < D1
+    uint32_t bad = 0x80000000u;  // bit 31: always-invalid marker for j >= PLANE4
+#pragma unroll
+    for (int h = 0; h < FH1; ++h) bad |= ((unsigned)(y0 - 1 + h) >= (unsigned)D1) ? (1u << h) : 0u;
+#pragma unroll
+    for (int h = 0; h < FH2; ++h) bad |= ((unsigned)(x0 - 1 + h) >= (unsigned)D2) ? (1u << (8 + h)) : 0u;
+    const int yx = (((y0 - 1) * D2 + (x0 - 1)) * Cin + cc * CK) * 4;
+    uint32_t voff[NJ];  // byte offset of column i inside a z-plane (or OOB)
+#pragma unroll
+    for (int i = 0; i < NJ; ++i) voff[i] = (cmask[i] & bad) ? OOB : (uint32_t)(rel[i] + yx);
+#pragma unroll
+    for (int hz = 0; hz < FH0; ++hz) {
+      const int gz = z0 - 1 + hz;
+      const bool pv = (unsigned)gz < (unsigned)D0;  // scalar
+      const int so = pv ? gz * plane_bytes : 0;
+#pragma unroll
+      for (int i = 0; i < NJ; ++i)
+        stg[hz * NJ + i] = as_f4(__builtin_amdgcn_raw_buffer_load_b128(rin, (int)(pv ? voff[i] : OOB), so, 0));
+    }
+  }
+  __device__ __forceinline__ void commit(float* lds, const float4 (&stg)[NLD]) const {
+    __syncthreads();  // every wave has finished reading the previous item's tile
+#pragma unroll
+    for (int i = 0; i < NJ; ++i) {
+      if (i < NJ - 1 || tid + 256 * i < PLANE4) {
+#pragma unroll
+        for (int hz = 0; hz < FH0; ++hz)
+          *reinterpret_cast<float4*>(&lds[ldsa[i] + hz * (FH1 * FH2 * CKP)]) = stg[hz * NJ + i];
+      }
+    }
+    __syncthreads();
+  }
+};
+
+// HaloStagerTile: one tile per workgroup of NTHR threads (HZ x HY x HX halo).  The tile is fixed, so the columns carry the tile
+// origin and their validity; the channel chunk, the parity origin and the z-plane travel in the scalar soffset.  `is` = 2 reads
+// one parity sub-lattice of a tensor of twice the extents (conv-grid voxel g -> tensor voxel g*is + parity).
+template <int HZ, int HY, int HX, int NTHR, int CK>
+struct HaloStagerTile {
+  static constexpr int CKP = CK + 4, C4 = CK / 4;
+  static constexpr int PL4 = HY * HX * C4, NJ = (PL4 + NTHR - 1) / NTHR, NLD = NJ * HZ;
+  // bit of local column hx in the validity mask, above the HY row bits: 8 for the 18-wide halo, 20 for the narrow brick halos
+  // (HY up to 10)
+  static constexpr int XB = HX > 12 ? 8 : 20;
+  static_assert(HY <= XB && XB + HX <= 32, "row and column bits share one 32-bit mask");
+  static constexpr uint32_t OOB = 0x80000000u;
+  __amdgpu_buffer_rsrc_t rin;
+  uint32_t vrel[NJ];
+  int ldsa[NJ];
+  int sZ, z0, D0, tid;
+
+  __device__ __forceinline__ HaloStagerTile(const float* in, int z0_, int y0, int x0, int D0_, int D1, int D2, int Cin, int is,
+                                            int tid_)
+      : z0(z0_), D0(D0_), tid(tid_) {
+    const int sX = is * Cin * 4, sY = is * (D2 * is) * Cin * 4;  // bytes
+    sZ = is * (D1 * is) * (D2 * is) * Cin * 4;
+    rin = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(in), 0, (int)((int64_t)D0 * D1 * D2 * is * is * is * Cin * 4),
+                                            0x00020000);
+    uint32_t bad = 0;
+#pragma unroll
+    for (int h = 0; h < HY; ++h) bad |= ((unsigned)(y0 - 1 + h) >= (unsigned)D1) ? (1u << h) : 0u;
+#pragma unroll
+    for (int h = 0; h < HX; ++h) bad |= ((unsigned)(x0 - 1 + h) >= (unsigned)D2) ? (1u << (XB + h)) : 0u;
+#pragma unroll
+    for (int i = 0; i < NJ; ++i) {
+      const int j = tid + NTHR * i;
+      const int hy = j / (HX * C4), r = j - hy * (HX * C4), hx = r / C4, c4 = r - hx * C4;
+      const bool ok = (j < PL4) && !(((1u << hy) | (1u << (XB + hx))) & bad);
+      vrel[i] = ok ? (uint32_t)((y0 - 1 + hy) * sY + (x0 - 1 + hx) * sX + c4 * 16) : OOB;
+      ldsa[i] = (hy * HX + hx) * CKP + c4 * 4;
+    }
+  }
+  // halo of channel chunk cc at parity origin pconst (bytes) -> staging registers
+  __device__ __forceinline__ void load_all(int cc, int pconst, float4 (&stg)[NLD]) const {
+#pragma unroll
+    for (int hz = 0; hz < HZ; ++hz) {
+      const int gz = z0 - 1 + hz;
+      const bool pv = (unsigned)gz < (unsigned)D0;
+      const int so = (pv ? gz * sZ : 0) + cc * (CK * 4) + pconst;
+#pragma unroll
+      for (int i = 0; i < NJ; ++i) stg[hz * NJ + i] = as_f4(__builtin_amdgcn_raw_buffer_load_b128(rin, (int)(pv ? vrel[i] : OOB), so, 0));
+    }
+  }
+  __device__ __forceinline__ void commit(float* lds, const float4 (&stg)[NLD]) const {
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < NJ; ++i) {
+      if (i < NJ - 1 || tid + NTHR * i < PL4) {
+#pragma unroll
+        for (int hz = 0; hz < HZ; ++hz) *reinterpret_cast<float4*>(&lds[ldsa[i] + hz * (HY * HX * CKP)]) = stg[hz * NJ + i];
+      }
+    }
+    __syncthreads();
+  }
+};
+
+// HaloStagerVox: the first layer's [648 voxels][CIN <= 2] halo tile.  One element per voxel, so thread t owns voxels
+// j = t + 256 i of the whole 6 x 6 x 18 tile and the validity mask has one bit per axis: (1 << hz) | (1 << (6 + hy)) |
+// (1 << (12 + hx)).
+template <int CIN>
+struct HaloStagerVox {
+  static constexpr int FH1 = 6, FHV = FH0 * FH1 * FH2, NS = (FHV + 255) / 256;
+  static constexpr uint32_t OOB = 0x80000000u;
+  __amdgpu_buffer_rsrc_t rin;
+  int rel[NS], ldsa[NS];
+  uint32_t cmask[NS];
+  int D0, D1, D2, tid;
+
+  __device__ __forceinline__ HaloStagerVox(const float* in, int D0_, int D1_, int D2_, int tid_)
+      : D0(D0_), D1(D1_), D2(D2_), tid(tid_) {
+    rin = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(in), 0, (int)((int64_t)D0 * D1 * D2 * CIN * 4), 0x00020000);
+#pragma unroll
+    for (int i = 0; i < NS; ++i) {
+      const int j = tid + 256 * i;
+      const int hz = j / (FH1 * FH2), hy = (j / FH2) % FH1, hx = j % FH2;
+      rel[i] = ((hz * D1 + hy) * D2 + hx) * CIN * 4;
+      ldsa[i] = j * CIN;
+      cmask[i] = j < FHV ? ((1u << hz) | (1u << (6 + hy)) | (1u << (12 + hx))) : 0xFFFFFFFFu;
+    }
+  }
+  __device__ __forceinline__ void load_all(int z0, int y0, int x0, float (&stg)[NS][CIN]) const {
+    uint32_t bad = 0x80000000u;
+#pragma unroll
+    for (int h = 0; h < FH0; ++h) bad |= ((unsigned)(z0 - 1 + h) >= (unsigned)D0) ? (1u << h) : 0u;
+#pragma unroll
+    for (int h = 0; h < FH1; ++h) bad |= ((unsigned)(y0 - 1 + h) >= (unsigned)D1) ? (1u << (6 + h)) : 0u;
+#pragma unroll
+    for (int h = 0; h < FH2; ++h) bad |= ((unsigned)(x0 - 1 + h) >= (unsigned)D2) ? (1u << (12 + h)) : 0u;
+    const int org = (((z0 - 1) * D1 + (y0 - 1)) * D2 + (x0 - 1)) * CIN * 4;
+#pragma unroll
+    for (int i = 0; i < NS; ++i) {
+      const int vo = (cmask[i] & bad) ? (int)OOB : rel[i] + org;
+      if constexpr (CIN == 2) {
+        const u32x2 v = __builtin_amdgcn_raw_buffer_load_b64(rin, vo, 0, 0);
+        stg[i][0] = __uint_as_float(v.x);
+        stg[i][1] = __uint_as_float(v.y);
+      } else {
+        stg[i][0] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rin, vo, 0, 0));
+      }
+    }
+  }
+  __device__ __forceinline__ void commit(float* lds, const float (&stg)[NS][CIN]) const {
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < NS; ++i) {
+      if (i < NS - 1 || tid + 256 * i < FHV) {
+#pragma unroll
+        for (int c = 0; c < CIN; ++c) lds[ldsa[i] + c] = stg[i][c];
+      }
+    }
+    __syncthreads();
+  }
+};
+
+// Iterations of one workgroup of the lean / brick forward kernels: (parity, channel chunk) pairs.  KSPLIT spreads the channel
+// chunks over gridDim.z workgroups; mode 1 (NTAPS = 8) takes its output parity from blockIdx.z; mode 2 sums 8 parity convs
+// into one output: all in this workgroup, or (small deep levels: too few tiles to fill the chip) split over gridDim.z
+// workgroups that accumulate with atomics onto a zeroed output (`psplit`).
+template <bool KSPLIT, int NTAPS>
+struct ParityIter {
+  static_assert(NTAPS == 27 || !KSPLIT, "parity convs are not split over K");
+  int mode, ncc, cc_lo, ncw, par_lo, opar, nit;
+  bool psplit;
+  int64_t wstride;
+  struct Item {
+    int cc, par;
+    int shz, shy, shx;  // position of the 2x2x2 window inside the 3x3x3 stencil (see up_tapmask): mode 1 shift = parity,
+    int shtap;          //   mode 2 (flipped taps) shift = 1 - parity; shtap = the window's first tap
+    int pconst;         // byte offset of the parity's sub-lattice origin in the 2x input tensor (mode 2)
+  };
+  __device__ __forceinline__ ParityIter(const ConvExt& ext, unsigned gridz, unsigned blockz, int ncc_) : ncc(ncc_) {
+    const int gz = (int)gridz, bz = (int)blockz;
+    mode = (NTAPS == 8) ? ext.mode : 0;
+    wstride = ext.wstride;
+    const int cpz = KSPLIT ? (ncc + gz - 1) / gz : ncc;
+    cc_lo = KSPLIT ? bz * cpz : 0;
+    ncw = min(ncc, cc_lo + cpz) - cc_lo;
+    psplit = (NTAPS == 8) && mode == 2 && gridz > 1;
+    const int npar = (mode == 2) ? 8 / gz : 1;
+    par_lo = (mode == 2) ? bz * npar : 0;
+    opar = (mode == 1) ? bz : 0;
+    nit = npar * ncw;
+  }
+  __device__ __forceinline__ Item at(int it, int D1, int D2, int Cin) const {
+    Item r;
+    const int ipar = it / ncw;
+    r.cc = cc_lo + it - ipar * ncw;
+    r.par = (mode == 1) ? opar : ipar + par_lo;
+    const int pz = (r.par >> 2) & 1, py = (r.par >> 1) & 1, px = r.par & 1;
+    r.shz = (NTAPS == 8) ? (mode == 2 ? 1 - pz : pz) : 0;
+    r.shy = (NTAPS == 8) ? (mode == 2 ? 1 - py : py) : 0;
+    r.shx = (NTAPS == 8) ? (mode == 2 ? 1 - px : px) : 0;
+    r.shtap = (r.shz * 3 + r.shy) * 3 + r.shx;
+    r.pconst = (mode == 2) ? ((pz * (D1 * 2) + py) * (D2 * 2) + px) * Cin * 4 : 0;
+    return r;
+  }
+  // scalar byte offset of the packed weights of (n-tile group nc, item): TAPB bytes per tap
+  __device__ __forceinline__ int wsoff(const Item& r, int nc, int TAPB) const {
+    return (int)(((int64_t)(nc * ncc + r.cc) * 27 + r.shtap) * TAPB + (int64_t)r.par * wstride * 4);
+  }
+  // i-th tap of an iteration, relative to shtap
+  static __host__ __device__ constexpr int tap_id(int i) {
+    return NTAPS == 27 ? i : ((i >> 2) & 1) * 9 + ((i >> 1) & 1) * 3 + (i & 1);
+  }
+};
+
+// one float4 (channels 4g .. 4g+3) of the Cout = 24 epilogue of the 4x4x1 forward kernels: bias, addend (DY: or the fused
+// activation backward of the producing layer, act 2, addend = its output), activation
+template <bool RELU, bool DY>
+__device__ __forceinline__ float4 p4_epilogue_value(const f32x4& a, const float (&bv)[24], int g, const float* addend, size_t o,
+                                                    int act) {
+  float4 v = make_float4(a[0], a[1], a[2], a[3]);
+  v.x += bv[4 * g];
+  v.y += bv[4 * g + 1];
+  v.z += bv[4 * g + 2];
+  v.w += bv[4 * g + 3];
+  if (DY && act == 2) {
+    const float4 y = *reinterpret_cast<const float4*>(addend + o + 4 * g);
+    v.x *= act_dy<RELU>(y.x);
+    v.y *= act_dy<RELU>(y.y);
+    v.z *= act_dy<RELU>(y.z);
+    v.w *= act_dy<RELU>(y.w);
+  } else if (addend) {  // indexed like out; may alias it: same element read and written by this lane
+    const float4 y = *reinterpret_cast<const float4*>(addend + o + 4 * g);
+    v.x += y.x;
+    v.y += y.y;
+    v.z += y.z;
+    v.w += y.w;
+  }
+  if (act == 1) {
+    v.x = act_f<RELU>(v.x);
+    v.y = act_f<RELU>(v.y);
+    v.z = act_f<RELU>(v.z);
+    v.w = act_f<RELU>(v.w);
+  }
+  return v;
+}
+
 template <int CK, int NT, int MT, bool KSPLIT, bool RELU = false>
 __global__ __launch_bounds__(256, 2) void conv3d_fwd_kernel(const float* __restrict__ in, const float* __restrict__ wp,
                                                             const float* __restrict__ bias, float* __restrict__ out,
@@ -421,14 +737,7 @@ __global__ __launch_bounds__(256, 2) void conv3d_fwd_kernel(const float* __restr
   constexpr int NCG = CK / 8;
   constexpr int C4 = CK / 4;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  // XCD-aware tile order: workgroup b runs on XCD b%8 (observed dispatch order, speed only); give every XCD a
-  // contiguous range of tiles so that neighbouring tiles (shared halos) hit the same L2.  Bijective for any grid.
-  int t;
-  {
-    const int nwg = gridDim.x, b = blockIdx.x;
-    const int q = nwg >> 3, r = nwg & 7, xcd = b & 7, j = b >> 3;
-    t = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + j;
-  }
+  int t = xcd_tile_pos();
   const int t2 = t % tiles2;
   t /= tiles2;
   const int t1 = t % tiles1;
@@ -622,24 +931,18 @@ __global__ __launch_bounds__(256, 2) void conv3d_fwd_persist_kernel(const float*
   const int li = lane & 15, kq = lane >> 4;
   const int nc = blockIdx.y;
   const int nitems = ntiles * ncc;
-  // XCD-aware order: in every round of gridDim.x items, workgroup b (XCD b%8) takes position (b%8)*(G/8) + b/8,
-  // so each XCD's L2 serves a contiguous run of neighbouring tiles.  gridDim.x is a multiple of 8.
   const int G = gridDim.x;
-  const int my_pos = (blockIdx.x & 7) * (G >> 3) + (blockIdx.x >> 3);
+  const int my_pos = xcd_start_pos();
 
   int a_base[MT];
 #pragma unroll
   for (int m = 0; m < MT; ++m) a_base[m] = ((wave * FH1 + m) * FH2 + li) * CKP + 2 * kq;
   const float* wl = wp + (size_t)nc * ncc * 27 * NCG * NT * 128 + lane * 2;
 
-  // ---- VALU-lean addressing.  On CDNA4 every vector-ALU instruction takes ~3-4 cycles out of the SIMD's MFMA issue
-  // (tools/ubench/mfma_issue.hip), so the per-item address arithmetic is moved to the scalar unit:
-  //  * halo staging: in every z-plane of the 6x6x18 halo tile, thread t owns the same <= 3 (y, x, channel-quad) columns
-  //    j = t + 256 i of the plane's 648 float4.  Their byte offsets relative to the tile origin and their LDS addresses
-  //    are computed ONCE per kernel; per item only `offset + scalar` and a bit-mask validity test remain.  The loads are
-  //    raw buffer loads: soffset carries the z-plane (scalar), out-of-volume elements get an offset beyond
-  //    num_records and come back as zeros (hardware range check) -- no per-element clamping or selects.
-  //  * B fragments: buffer loads with voffset = lane*8, soffset = scalar (chunk, tap), immediate = (g, n).
+  // ---- VALU-lean addressing: the halo staging of HaloStagerWalk (see there), written out in this kernel, in
+  // conv3d_fwd_p4_kernel and in conv3d_up_fwd_p4_kernel because the shared struct cost them vector registers / a scalar
+  // spill (profiles/conv3d_stager_refactor_asm.txt); a change to the range-check trick or the LDS layout goes to all four.
+  // B fragments: buffer loads with voffset = lane*8, soffset = scalar (chunk, tap), immediate = (g, n) (bload).
   constexpr int PLANE4 = FH1 * FH2 * C4;  // 648 float4 per halo z-plane
   constexpr int NJ = (PLANE4 + 255) / 256;  // 3 columns per thread
   constexpr int NLD = NJ * FH0;             // 18 halo loads per item
@@ -682,17 +985,6 @@ __global__ __launch_bounds__(256, 2) void conv3d_fwd_persist_kernel(const float*
     const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rin, (int)vo, so, 0);
     return make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w));
   };
-  auto tile_origin = [&](int t, int& z0, int& y0, int& x0) {
-    const int t2 = t % tiles2, t1 = (t / tiles2) % tiles1, t0 = t / (tiles2 * tiles1);
-    z0 = t0 * FT0;
-    y0 = t1 * FT1;
-    x0 = t2 * FT2;
-  };
-  auto bload = [&](int soff, int idx) -> float2 {  // idx = g*NT + n; immediates stay below 4096
-    const int hi = idx >> 2, lo = idx & 3;
-    const u32x2 v = __builtin_amdgcn_raw_buffer_load_b64(rw, lane * 8 + lo * 512, soff + hi * 2048, 0);
-    return make_float2(__uint_as_float(v.x), __uint_as_float(v.y));
-  };
 
   f32x4 acc[MT][NT];
   float4 stg[NLD];
@@ -702,7 +994,7 @@ __global__ __launch_bounds__(256, 2) void conv3d_fwd_persist_kernel(const float*
   if (tile >= ntiles) return;
   (void)nitems;
   int z0, y0, x0, cc = 0;
-  tile_origin(tile, z0, y0, x0);
+  tile_origin<FT1>(tile, tiles1, tiles2, z0, y0, x0);
   {
     uint32_t voff[NJ];
     item_offsets(y0, x0, cc, voff);
@@ -715,7 +1007,7 @@ __global__ __launch_bounds__(256, 2) void conv3d_fwd_persist_kernel(const float*
     const int ntile = (cc + 1 < ncc) ? tile : tile + G;
     const bool has_next = ntile < ntiles;
     int nz0 = z0, ny0 = y0, nx0 = x0;
-    if (has_next && ntile != tile) tile_origin(ntile, nz0, ny0, nx0);
+    if (has_next && ntile != tile) tile_origin<FT1>(ntile, tiles1, tiles2, nz0, ny0, nx0);
     uint32_t nvoff[NJ];
     item_offsets(ny0, nx0, ncc_, nvoff);
     if (cc == 0) {
@@ -743,7 +1035,7 @@ __global__ __launch_bounds__(256, 2) void conv3d_fwd_persist_kernel(const float*
 #pragma unroll
     for (int g = 0; g < NCG; ++g)
 #pragma unroll
-      for (int n = 0; n < NT; ++n) bb[0][g][n] = bload(wsoff, g * NT + n);
+      for (int n = 0; n < NT; ++n) bb[0][g][n] = bload(rw, lane, wsoff, g * NT + n);
 #pragma unroll
     for (int m = 0; m < MT; ++m) aa[0][m] = *reinterpret_cast<const float2*>(&lds[a_base[m]]);
 
@@ -753,7 +1045,7 @@ __global__ __launch_bounds__(256, 2) void conv3d_fwd_persist_kernel(const float*
 #pragma unroll
         for (int g = 0; g < NCG; ++g)
 #pragma unroll
-          for (int n = 0; n < NT; ++n) bb[(tap + 1) & 1][g][n] = bload(wsoff + (tap + 1) * (NCG * NT * 512), g * NT + n);
+          for (int n = 0; n < NT; ++n) bb[(tap + 1) & 1][g][n] = bload(rw, lane, wsoff + (tap + 1) * (NCG * NT * 512), g * NT + n);
       }
       if (tap < NLD) {
         if (has_next) stg[tap] = halo_load(tap, nz0, nvoff);  // wave-uniform branch
@@ -820,7 +1112,7 @@ __global__ __launch_bounds__(256, 2) void conv3d_fwd_p4_kernel(const float* __re
   constexpr int CKP = CK + 4, C4 = CK / 4;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int G = gridDim.x;
-  const int my_pos = (blockIdx.x & 7) * (G >> 3) + (blockIdx.x >> 3);
+  const int my_pos = xcd_start_pos();
   const int vy = lane >> 4, vx = lane & 15;
   const int xbase = ((wave * FH1 + vy) * FH2 + vx) * CKP;
 
@@ -858,15 +1150,6 @@ __global__ __launch_bounds__(256, 2) void conv3d_fwd_p4_kernel(const float* __re
     const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rin, (int)(pv ? voff[i] : OOB), pv ? gz * plane_bytes : 0, 0);
     return make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w));
   };
-  auto tile_origin = [&](int t, int& z0, int& y0, int& x0) {
-    const int t2 = t % tiles2, t1 = (t / tiles2) % tiles1, t0 = t / (tiles2 * tiles1);
-    z0 = t0 * FT0;
-    y0 = t1 * FT1;
-    x0 = t2 * FT2;
-  };
-  auto wload = [&](int soff, int r) -> float {
-    return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rw, lane * 4 + r * 256, soff, 0));
-  };
 
   f32x4 acc[6];
   // results are stored from these registers, which nothing else touches until the next epilogue: re-zeroing `acc` (or
@@ -888,7 +1171,7 @@ __global__ __launch_bounds__(256, 2) void conv3d_fwd_p4_kernel(const float* __re
     return;
   }
   int z0, y0, x0, cc = 0;
-  tile_origin(tile, z0, y0, x0);
+  tile_origin<FT1>(tile, tiles1, tiles2, z0, y0, x0);
   {
     uint32_t voff[NJ];
     item_offsets(y0, x0, cc, voff);
@@ -901,8 +1184,8 @@ __global__ __launch_bounds__(256, 2) void conv3d_fwd_p4_kernel(const float* __re
   float wr[3][3];
 #pragma unroll
   for (int r = 0; r < 3; ++r) {
-    wr[0][r] = wload(0, r);
-    wr[1][r] = wload(768, r);
+    wr[0][r] = wload(rw, lane, 0, r);
+    wr[1][r] = wload(rw, lane, 768, r);
   }
 
   while (true) {
@@ -910,7 +1193,7 @@ __global__ __launch_bounds__(256, 2) void conv3d_fwd_p4_kernel(const float* __re
     const int ntile = (cc + 1 < ncc) ? tile : tile + G;
     const bool has_next = ntile < ntiles;
     int nz0 = z0, ny0 = y0, nx0 = x0;
-    if (has_next && ntile != tile) tile_origin(ntile, nz0, ny0, nx0);
+    if (has_next && ntile != tile) tile_origin<FT1>(ntile, tiles1, tiles2, nz0, ny0, nx0);
     uint32_t nvoff[NJ];
     item_offsets(ny0, nx0, ncc_, nvoff);
     if (cc == 0) {
@@ -938,10 +1221,10 @@ __global__ __launch_bounds__(256, 2) void conv3d_fwd_p4_kernel(const float* __re
       constexpr int toff = (((tap / 9) * FH1 + (tap / 3) % 3) * FH2 + tap % 3) * CKP;
       if constexpr (p + 2 < NP) {
 #pragma unroll
-        for (int r = 0; r < 3; ++r) wr[(p + 2) % 3][r] = wload(wsoff + (p + 2) * 768, r);
+        for (int r = 0; r < 3; ++r) wr[(p + 2) % 3][r] = wload(rw, lane, wsoff + (p + 2) * 768, r);
       } else {
 #pragma unroll
-        for (int r = 0; r < 3; ++r) wr[(p + 2) % 3][r] = wload(wsoff_n + (p + 2 - NP) * 768, r);
+        for (int r = 0; r < 3; ++r) wr[(p + 2) % 3][r] = wload(rw, lane, wsoff_n + (p + 2 - NP) * 768, r);
       }
       if constexpr (qp == 0 && tap < NLD) {
         if (has_next) stg[tap] = halo_load(tap, nz0, nvoff);  // wave-uniform branch
@@ -970,30 +1253,7 @@ __global__ __launch_bounds__(256, 2) void conv3d_fwd_p4_kernel(const float* __re
         const size_t o = (((size_t)gz * D1 + gy) * D2 + gx) * Cout;
 #pragma unroll
         for (int g = 0; g < 6; ++g) {
-          float4 v = make_float4(acc[g][0], acc[g][1], acc[g][2], acc[g][3]);
-          v.x += bv[4 * g];
-          v.y += bv[4 * g + 1];
-          v.z += bv[4 * g + 2];
-          v.w += bv[4 * g + 3];
-          if (act == 2) {  // fused ELU backward of the producing layer (addend = its output)
-            const float4 a = *reinterpret_cast<const float4*>(addend + o + 4 * g);
-            v.x *= act_dy<RELU>(a.x);
-            v.y *= act_dy<RELU>(a.y);
-            v.z *= act_dy<RELU>(a.z);
-            v.w *= act_dy<RELU>(a.w);
-          } else if (addend) {  // may alias out: same element read and written by this lane
-            const float4 a = *reinterpret_cast<const float4*>(addend + o + 4 * g);
-            v.x += a.x;
-            v.y += a.y;
-            v.z += a.z;
-            v.w += a.w;
-          }
-          if (act == 1) {
-            v.x = act_f<RELU>(v.x);
-            v.y = act_f<RELU>(v.y);
-            v.z = act_f<RELU>(v.z);
-            v.w = act_f<RELU>(v.w);
-          }
+          const float4 v = p4_epilogue_value<RELU, true>(acc[g], bv, g, addend, o, act);
           outreg[g] = v;
           if (stats_partial) {  // wave-uniform
             ps[4 * g] += v.x;
@@ -1057,7 +1317,7 @@ __global__ __launch_bounds__(256, 2) void conv3d_up_fwd_p4_kernel(const float* _
   constexpr int FT1 = MT, FH1 = MT + 2, CKP = CK + 4, C4 = CK / 4;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int G = gridDim.x;
-  const int my_pos = (blockIdx.x & 7) * (G >> 3) + (blockIdx.x >> 3);
+  const int my_pos = xcd_start_pos();
   const int vy = lane >> 4, vx = lane & 15;
   const int xbase = ((wave * FH1 + vy) * FH2 + vx) * CKP;
   constexpr int PLANE4 = FH1 * FH2 * C4, NJ = (PLANE4 + 255) / 256, NLD = NJ * FH0;
@@ -1077,12 +1337,6 @@ __global__ __launch_bounds__(256, 2) void conv3d_up_fwd_p4_kernel(const float* _
   }
   const int plane_bytes = D1 * D2 * Cin * 4;
   float4 stg[NLD];
-  auto tile_origin = [&](int t, int& z0, int& y0, int& x0) {
-    const int t2 = t % tiles2, t1 = (t / tiles2) % tiles1, t0 = t / (tiles2 * tiles1);
-    z0 = t0 * FT0;
-    y0 = t1 * FT1;
-    x0 = t2 * FT2;
-  };
   auto halo_loads = [&](int z0, int y0, int x0, int cc) {
     uint32_t bad = 0x80000000u;
 #pragma unroll
@@ -1104,9 +1358,6 @@ __global__ __launch_bounds__(256, 2) void conv3d_up_fwd_p4_kernel(const float* _
       }
     }
   };
-  auto wload = [&](int soff, int r) -> float {
-    return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rw, lane * 4 + r * 256, soff, 0));
-  };
   float bv[24];
 #pragma unroll
   for (int c = 0; c < 24; ++c) bv[c] = bias ? bias[c] : 0.f;
@@ -1115,7 +1366,7 @@ __global__ __launch_bounds__(256, 2) void conv3d_up_fwd_p4_kernel(const float* _
   int tile = my_pos;
   if (tile >= ntiles) return;
   int z0, y0, x0;
-  tile_origin(tile, z0, y0, x0);
+  tile_origin<FT1>(tile, tiles1, tiles2, z0, y0, x0);
   halo_loads(z0, y0, x0, 0);
   const int nsub = 2 * ncc;  // items of one tile: (pz, cc)
   int sub = 0;
@@ -1126,7 +1377,7 @@ __global__ __launch_bounds__(256, 2) void conv3d_up_fwd_p4_kernel(const float* _
     const int ntile = (sub + 1 < nsub) ? tile : tile + G;
     const bool has_next = ntile < ntiles;
     int nz0 = z0, ny0 = y0, nx0 = x0;
-    if (has_next && ntile != tile) tile_origin(ntile, nz0, ny0, nx0);
+    if (has_next && ntile != tile) tile_origin<FT1>(ntile, tiles1, tiles2, nz0, ny0, nx0);
     if (cc == 0) {
 #pragma unroll
       for (int q = 0; q < 4; ++q)
@@ -1159,15 +1410,15 @@ __global__ __launch_bounds__(256, 2) void conv3d_up_fwd_p4_kernel(const float* _
     float4 xq[2];
 #pragma unroll
     for (int r = 0; r < 3; ++r) {
-      wr[0][r] = wload(wsoff(0), r);
-      wr[1][r] = wload(wsoff(1), r);
+      wr[0][r] = wload(rw, lane, wsoff(0), r);
+      wr[1][r] = wload(rw, lane, wsoff(1), r);
     }
     xq[0] = *reinterpret_cast<const float4*>(&lds[xb]);
     sfor<0, NP>([&](auto P) {
       constexpr int p = decltype(P)::value, q = p / 24;
       if constexpr (p + 2 < NP) {
 #pragma unroll
-        for (int r = 0; r < 3; ++r) wr[(p + 2) % 3][r] = wload(wsoff(p + 2), r);
+        for (int r = 0; r < 3; ++r) wr[(p + 2) % 3][r] = wload(rw, lane, wsoff(p + 2), r);
       }
       sfor<0, 2>([&](auto H) {
         constexpr int h = decltype(H)::value, sidx = p * 2 + h;
@@ -1192,24 +1443,8 @@ __global__ __launch_bounds__(256, 2) void conv3d_up_fwd_p4_kernel(const float* _
         for (int q = 0; q < 4; ++q) {
           const size_t o = (((size_t)(2 * gz + pz) * (2 * D1) + (2 * gy + (q >> 1))) * (2 * D2) + (2 * gx + (q & 1))) * Cout;
 #pragma unroll
-          for (int g = 0; g < 6; ++g) {
-            float4 v = make_float4(acc[q][g][0] + bv[4 * g], acc[q][g][1] + bv[4 * g + 1], acc[q][g][2] + bv[4 * g + 2],
-                                   acc[q][g][3] + bv[4 * g + 3]);
-            if (addend) {  // indexed like out; may alias it
-              const float4 a = *reinterpret_cast<const float4*>(addend + o + 4 * g);
-              v.x += a.x;
-              v.y += a.y;
-              v.z += a.z;
-              v.w += a.w;
-            }
-            if (act == 1) {
-              v.x = act_f<RELU>(v.x);
-              v.y = act_f<RELU>(v.y);
-              v.z = act_f<RELU>(v.z);
-              v.w = act_f<RELU>(v.w);
-            }
-            *reinterpret_cast<float4*>(out + o + 4 * g) = v;
-          }
+          for (int g = 0; g < 6; ++g)
+            *reinterpret_cast<float4*>(out + o + 4 * g) = p4_epilogue_value<RELU, false>(acc[q][g], bv, g, addend, o, act);
         }
       }
     }
@@ -1232,67 +1467,30 @@ __global__ __launch_bounds__(256, 2) void conv3d_fwd_c2_kernel(const float* __re
                                                                int D0, int D1, int D2, int tiles1, int tiles2, int ntiles,
                                                                int act) {
   __shared__ __attribute__((aligned(16))) float lds[FH0 * 6 * FH2 * CIN];
-  constexpr int FH1 = 6, FHV = FH0 * FH1 * FH2, NS = (FHV + 255) / 256, Cout = 24;
+  using Stager = HaloStagerVox<CIN>;
+  constexpr int FH1 = Stager::FH1, Cout = 24;
   __shared__ __attribute__((aligned(16))) float otile[4 * 64 * Cout];  // output staging: [wave][voxel 64][24]
   constexpr int NG = 27 * CIN * 6, NR = (NG + 15) / 16;
-  constexpr uint32_t OOB = 0x80000000u;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int vy = lane >> 4, vx = lane & 15;
   const int xbase = ((wave * FH1 + vy) * FH2 + vx) * CIN;
   float wr[NR];
 #pragma unroll
   for (int r = 0; r < NR; ++r) wr[r] = wp[r * 64 + lane];
-  const __amdgpu_buffer_rsrc_t rin =
-      __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(in), 0, (int)((int64_t)D0 * D1 * D2 * CIN * 4), 0x00020000);
-  int rel[NS], ldsa[NS];
-  uint32_t cmask[NS];
-#pragma unroll
-  for (int i = 0; i < NS; ++i) {
-    const int j = tid + 256 * i;
-    const int hz = j / (FH1 * FH2), hy = (j / FH2) % FH1, hx = j % FH2;
-    rel[i] = ((hz * D1 + hy) * D2 + hx) * CIN * 4;
-    ldsa[i] = j * CIN;
-    cmask[i] = j < FHV ? ((1u << hz) | (1u << (6 + hy)) | (1u << (12 + hx))) : 0xFFFFFFFFu;
-  }
-  float stg[NS][CIN];
+  const Stager hs(in, D0, D1, D2, tid);
+  float stg[Stager::NS][CIN];
   auto load_tile = [&](int t) {
-    const int t2 = t % tiles2, t1 = (t / tiles2) % tiles1, t0 = t / (tiles2 * tiles1);
-    const int z0 = t0 * FT0, y0 = t1 * 4, x0 = t2 * FT2;
-    uint32_t bad = 0x80000000u;
-#pragma unroll
-    for (int h = 0; h < FH0; ++h) bad |= ((unsigned)(z0 - 1 + h) >= (unsigned)D0) ? (1u << h) : 0u;
-#pragma unroll
-    for (int h = 0; h < FH1; ++h) bad |= ((unsigned)(y0 - 1 + h) >= (unsigned)D1) ? (1u << (6 + h)) : 0u;
-#pragma unroll
-    for (int h = 0; h < FH2; ++h) bad |= ((unsigned)(x0 - 1 + h) >= (unsigned)D2) ? (1u << (12 + h)) : 0u;
-    const int org = (((z0 - 1) * D1 + (y0 - 1)) * D2 + (x0 - 1)) * CIN * 4;
-#pragma unroll
-    for (int i = 0; i < NS; ++i) {
-      const int vo = (cmask[i] & bad) ? (int)OOB : rel[i] + org;
-      if constexpr (CIN == 2) {
-        const u32x2 v = __builtin_amdgcn_raw_buffer_load_b64(rin, vo, 0, 0);
-        stg[i][0] = __uint_as_float(v.x);
-        stg[i][1] = __uint_as_float(v.y);
-      } else {
-        stg[i][0] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rin, vo, 0, 0));
-      }
-    }
+    int z0, y0, x0;
+    tile_origin<4>(t, tiles1, tiles2, z0, y0, x0);
+    hs.load_all(z0, y0, x0, stg);
   };
   const int G = gridDim.x;
-  const int my_pos = (blockIdx.x & 7) * (G >> 3) + (blockIdx.x >> 3);
+  const int my_pos = xcd_start_pos();
   if (my_pos < ntiles) load_tile(my_pos);
   for (int t = my_pos; t < ntiles; t += G) {
-    const int t2 = t % tiles2, t1 = (t / tiles2) % tiles1, t0 = t / (tiles2 * tiles1);
-    const int z0 = t0 * FT0, y0 = t1 * 4, x0 = t2 * FT2;
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < NS; ++i) {
-      if (i < NS - 1 || tid + 256 * i < FHV) {
-#pragma unroll
-        for (int c = 0; c < CIN; ++c) lds[ldsa[i] + c] = stg[i][c];
-      }
-    }
-    __syncthreads();
+    int z0, y0, x0;
+    tile_origin<4>(t, tiles1, tiles2, z0, y0, x0);
+    hs.commit(lds, stg);
     if (t + G < ntiles) load_tile(t + G);
     f32x4 acc[6];
 #pragma unroll
@@ -1366,24 +1564,17 @@ __global__ __launch_bounds__(256, 2) void conv3d_fwd_lean_kernel(const float* __
                                                                  int D0, int D1, int D2, int Cin, int Cout, int ncc,
                                                                  int tiles1, int tiles2, int act, ConvExt ext) {
   extern __shared__ __attribute__((aligned(16))) float lds[];  // [FHV][CKP]
-  constexpr int CK = 24, FT1 = MT, FH1 = MT + 2, CKP = CK + 4, NCG = CK / 8, C4 = CK / 4;
-  constexpr int PL4 = FH1 * FH2 * C4, NJ = (PL4 + 255) / 256, NLD = NJ * FH0;
-  constexpr uint32_t OOB = 0x80000000u;
-  static_assert(NTAPS == 27 || !KSPLIT, "parity convs are not split over K");
+  constexpr int CK = 24, FT1 = MT, FH1 = MT + 2, CKP = CK + 4, NCG = CK / 8;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  int t;
-  {
-    const int nwg = gridDim.x, b = blockIdx.x;
-    const int q = nwg >> 3, r = nwg & 7, xcd = b & 7, j = b >> 3;
-    t = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + j;
-  }
+  int t = xcd_tile_pos();
   const int t2 = t % tiles2;
   t /= tiles2;
   const int t1 = t % tiles1;
   const int t0 = t / tiles1;
   const int z0 = t0 * FT0, y0 = t1 * FT1, x0 = t2 * FT2;
   const int nc = blockIdx.y;
-  const int mode = (NTAPS == 8) ? ext.mode : 0;
+  const ParityIter<KSPLIT, NTAPS> pit(ext, gridDim.z, blockIdx.z, ncc);
+  const int mode = pit.mode, opar = pit.opar;
 
   f32x4 acc[MT][NT];
 #pragma unroll
@@ -1397,103 +1588,40 @@ __global__ __launch_bounds__(256, 2) void conv3d_fwd_lean_kernel(const float* __
 
   // input view: conv-grid voxel g -> tensor voxel g*is + io (mode 2 reads one parity sub-lattice of the 2x tensor)
   const int is = (mode == 2) ? 2 : 1;
-  const int sX = is * Cin * 4, sY = is * (D2 * is) * Cin * 4, sZ = is * (D1 * is) * (D2 * is) * Cin * 4;  // bytes
-  const __amdgpu_buffer_rsrc_t rin = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<float*>(in), 0, (int)((int64_t)D0 * D1 * D2 * is * is * is * Cin * 4), 0x00020000);
+  using Stager = HaloStagerTile<FH0, FH1, FH2, 256, CK>;
+  const Stager hs(in, z0, y0, x0, D0, D1, D2, Cin, is, tid);
   const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(wp), 0, 0x7FFFFFF0, 0x00020000);
-  uint32_t vrel[NJ];
-  int ldsa[NJ];
-  {
-    uint32_t bad = 0;
-#pragma unroll
-    for (int h = 0; h < FH1; ++h) bad |= ((unsigned)(y0 - 1 + h) >= (unsigned)D1) ? (1u << h) : 0u;
-#pragma unroll
-    for (int h = 0; h < FH2; ++h) bad |= ((unsigned)(x0 - 1 + h) >= (unsigned)D2) ? (1u << (8 + h)) : 0u;
-#pragma unroll
-    for (int i = 0; i < NJ; ++i) {
-      const int j = tid + 256 * i;
-      const int hy = j / (FH2 * C4), r = j - hy * (FH2 * C4), hx = r / C4, c4 = r - hx * C4;
-      const bool ok = (j < PL4) && !(((1u << hy) | (1u << (8 + hx))) & bad);
-      vrel[i] = ok ? (uint32_t)((y0 - 1 + hy) * sY + (x0 - 1 + hx) * sX + c4 * 16) : OOB;
-      ldsa[i] = (hy * FH2 + hx) * CKP + c4 * 4;
-    }
-  }
   constexpr int TAPB = NCG * NT * 512;  // bytes of packed weights per tap
-  auto bload = [&](int soff, int idx) -> float2 {
-    const int hi = idx >> 2, lo = idx & 3;
-    const u32x2 v = __builtin_amdgcn_raw_buffer_load_b64(rw, lane * 8 + lo * 512, soff + hi * 2048, 0);
-    return make_float2(__uint_as_float(v.x), __uint_as_float(v.y));
-  };
-
-  const int cpz = KSPLIT ? (ncc + (int)gridDim.z - 1) / (int)gridDim.z : ncc;
-  const int cc_lo = KSPLIT ? (int)blockIdx.z * cpz : 0;
-  const int cc_hi = min(ncc, cc_lo + cpz);
-  // mode 2 sums 8 parity convs into one output: all in this workgroup, or (small deep levels: too few tiles to fill
-  // the chip) split over gridDim.z workgroups that accumulate with atomics onto a zeroed output
-  const bool psplit = (NTAPS == 8) && mode == 2 && gridDim.z > 1;
-  const int npar = (mode == 2) ? 8 / (int)gridDim.z : 1;
-  const int par_lo = (mode == 2) ? (int)blockIdx.z * npar : 0;
-  const int opar = (mode == 1) ? (int)blockIdx.z : 0;
-  // halo of iteration `it` (parity, chunk) -> staging registers; issued one iteration ahead so that the loads complete
-  // behind the MFMAs of the previous chunk
-  const int nit = npar * (cc_hi - cc_lo);
-  float4 stg[NLD];
-  auto halo_loads = [&](int it) {
-    const int ipar = it / (cc_hi - cc_lo);
-    const int cc = cc_lo + it - ipar * (cc_hi - cc_lo);
-    const int par = (mode == 1) ? opar : ipar + par_lo;
-    const int pconst = (mode == 2) ? ((((par >> 2) & 1) * (D1 * 2) + ((par >> 1) & 1)) * (D2 * 2) + (par & 1)) * Cin * 4 : 0;
-#pragma unroll
-    for (int hz = 0; hz < FH0; ++hz) {
-      const int gz = z0 - 1 + hz;
-      const bool pv = (unsigned)gz < (unsigned)D0;
-      const int so = (pv ? gz * sZ : 0) + cc * (CK * 4) + pconst;
-#pragma unroll
-      for (int i = 0; i < NJ; ++i) {
-        const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rin, (int)(pv ? vrel[i] : OOB), so, 0);
-        stg[hz * NJ + i] = make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w));
-      }
-    }
-  };
-  if (nit > 0) halo_loads(0);
+  const bool psplit = pit.psplit;
+  const int nit = pit.nit;
+  // the halo of iteration it + 1 (parity, chunk) goes to the staging registers one iteration ahead, so that the loads
+  // complete behind the MFMAs of the previous chunk
+  float4 stg[Stager::NLD];
+  if (nit > 0) {
+    const auto first = pit.at(0, D1, D2, Cin);
+    hs.load_all(first.cc, first.pconst, stg);
+  }
   for (int it = 0; it < nit; ++it) {
-    const int ipar = it / (cc_hi - cc_lo);
-    const int cc = cc_lo + it - ipar * (cc_hi - cc_lo);
-    const int par = (mode == 1) ? opar : ipar + par_lo;
-    const int pz = (par >> 2) & 1, py = (par >> 1) & 1, px = par & 1;
-    // position of the 2x2x2 window inside the 3x3x3 stencil (see up_tapmask): mode 1 shift = parity, mode 2 (flipped
-    // taps) shift = 1 - parity
-    const int shz = (NTAPS == 8) ? (mode == 2 ? 1 - pz : pz) : 0, shy = (NTAPS == 8) ? (mode == 2 ? 1 - py : py) : 0,
-              shx = (NTAPS == 8) ? (mode == 2 ? 1 - px : px) : 0;
-    const int shtap = (shz * 3 + shy) * 3 + shx;
-    const int shlds = ((shz * FH1 + shy) * FH2 + shx) * CKP;
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < NJ; ++i) {
-      if (i < NJ - 1 || tid + 256 * i < PL4) {
-#pragma unroll
-        for (int hz = 0; hz < FH0; ++hz)
-          *reinterpret_cast<float4*>(&lds[ldsa[i] + hz * (FH1 * FH2 * CKP)]) = stg[hz * NJ + i];
-      }
+    const auto cur = pit.at(it, D1, D2, Cin);
+    const int shlds = ((cur.shz * FH1 + cur.shy) * FH2 + cur.shx) * CKP;
+    hs.commit(lds, stg);
+    if (it + 1 < nit) {
+      const auto next = pit.at(it + 1, D1, D2, Cin);
+      hs.load_all(next.cc, next.pconst, stg);
     }
-    __syncthreads();
-    if (it + 1 < nit) halo_loads(it + 1);
 
-    const int wsoff = (int)(((int64_t)(nc * ncc + cc) * 27 + shtap) * TAPB + (int64_t)par * ext.wstride * 4);
+    const int wsoff = pit.wsoff(cur, nc, TAPB);
     int ab[MT];
 #pragma unroll
     for (int m = 0; m < MT; ++m) ab[m] = a_base[m] + shlds;
-    auto tap_id = [](int i) { return NTAPS == 27 ? i : ((i >> 2) & 1) * 9 + ((i >> 1) & 1) * 3 + (i & 1); };
-    auto tap_lds = [&](int i) {
-      const int tt = tap_id(i);
-      return (((tt / 9) * FH1 + (tt / 3) % 3) * FH2 + tt % 3) * CKP;
-    };
+    auto tap_id = [](int i) { return ParityIter<KSPLIT, NTAPS>::tap_id(i); };
+    auto tap_lds = [](int i) { return tap_halo_off<FH1, FH2, CKP>(ParityIter<KSPLIT, NTAPS>::tap_id(i)); };
     float2 bb[2][NCG][NT];
     float2 aa[2][MT];
 #pragma unroll
     for (int g = 0; g < NCG; ++g)
 #pragma unroll
-      for (int n = 0; n < NT; ++n) bb[0][g][n] = bload(wsoff + tap_id(0) * TAPB, g * NT + n);
+      for (int n = 0; n < NT; ++n) bb[0][g][n] = bload(rw, lane, wsoff + tap_id(0) * TAPB, g * NT + n);
 #pragma unroll
     for (int m = 0; m < MT; ++m) aa[0][m] = *reinterpret_cast<const float2*>(&lds[ab[m] + tap_lds(0)]);
 #pragma unroll
@@ -1502,7 +1630,7 @@ __global__ __launch_bounds__(256, 2) void conv3d_fwd_lean_kernel(const float* __
 #pragma unroll
         for (int g = 0; g < NCG; ++g)
 #pragma unroll
-          for (int n = 0; n < NT; ++n) bb[(ti + 1) & 1][g][n] = bload(wsoff + tap_id(ti + 1) * TAPB, g * NT + n);
+          for (int n = 0; n < NT; ++n) bb[(ti + 1) & 1][g][n] = bload(rw, lane, wsoff + tap_id(ti + 1) * TAPB, g * NT + n);
       }
       const int toff = tap_lds(ti);
       const int toff_n = tap_lds(ti + 1 < NTAPS ? ti + 1 : ti);
@@ -1579,11 +1707,9 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void conv3d_fwd_brick_kernel(const
                                                                   int D0, int D1, int D2, int Cin, int Cout, int ncc,
                                                                   int tiles1, int tiles2, int act, ConvExt ext) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  constexpr int CK = 24, CKP = CK + 4, NCG = CK / 8, C4 = CK / 4, MT = 4;
+  constexpr int CK = 24, CKP = CK + 4, NCG = CK / 8, MT = 4;
   constexpr int NTHR = 64 * WM * WN, TZ = 4, TY = 4 * WM, TX = 4;  // tile in voxels
   constexpr int HZ = TZ + 2, HY = TY + 2, HX = TX + 2;
-  constexpr int PL4 = HY * HX * C4, NJ = (PL4 + NTHR - 1) / NTHR, NLD = NJ * HZ;
-  constexpr uint32_t OOB = 0x80000000u;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave / WN, wn = wave % WN;
   int t = blockIdx.x;
@@ -1593,8 +1719,8 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void conv3d_fwd_brick_kernel(const
   const int t0 = t / tiles1;
   const int z0 = t0 * TZ, y0 = t1 * TY, x0 = t2 * TX;
   const int nc = blockIdx.y * WN + wn;  // this wave's group of NT n-tiles
-  static_assert(NTAPS == 27 || !KSPLIT, "parity convs are not split over K");
-  const int mode = (NTAPS == 8) ? ext.mode : 0;  // 1: up-forward (parity = blockIdx.z), 2: up-data-gradient (8 parities)
+  const ParityIter<KSPLIT, NTAPS> pit(ext, gridDim.z, blockIdx.z, ncc);
+  const int mode = pit.mode, opar = pit.opar;  // 1: up-forward (parity = blockIdx.z), 2: up-data-gradient (8 parities)
   const float* addend = ext.addend;
 
   f32x4 acc[MT][NT];
@@ -1609,96 +1735,38 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void conv3d_fwd_brick_kernel(const
   for (int m = 0; m < MT; ++m) a_base[m] = ((m * HY + wm * 4 + (li >> 2)) * HX + (li & 3)) * CKP + 2 * kq;
 
   const int is = (mode == 2) ? 2 : 1;  // input view: conv-grid voxel g -> tensor voxel g*is + parity
-  const int sX = is * Cin * 4, sY = is * (D2 * is) * Cin * 4, sZ = is * (D1 * is) * (D2 * is) * Cin * 4;  // bytes
-  const __amdgpu_buffer_rsrc_t rin = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<float*>(in), 0, (int)((int64_t)D0 * D1 * D2 * is * is * is * Cin * 4), 0x00020000);
+  using Stager = HaloStagerTile<HZ, HY, HX, NTHR, CK>;
+  const Stager hs(in, z0, y0, x0, D0, D1, D2, Cin, is, tid);
   const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(wp), 0, 0x7FFFFFF0, 0x00020000);
-  uint32_t vrel[NJ];
-  int ldsa[NJ];
-  {
-    uint32_t bad = 0;
-#pragma unroll
-    for (int h = 0; h < HY; ++h) bad |= ((unsigned)(y0 - 1 + h) >= (unsigned)D1) ? (1u << h) : 0u;
-#pragma unroll
-    for (int h = 0; h < HX; ++h) bad |= ((unsigned)(x0 - 1 + h) >= (unsigned)D2) ? (1u << (20 + h)) : 0u;
-#pragma unroll
-    for (int i = 0; i < NJ; ++i) {
-      const int j = tid + NTHR * i;
-      const int hy = j / (HX * C4), r = j - hy * (HX * C4), hx = r / C4, c4 = r - hx * C4;
-      const bool ok = (j < PL4) && !(((1u << hy) | (1u << (20 + hx))) & bad);
-      vrel[i] = ok ? (uint32_t)((y0 - 1 + hy) * sY + (x0 - 1 + hx) * sX + c4 * 16) : OOB;
-      ldsa[i] = (hy * HX + hx) * CKP + c4 * 4;
-    }
-  }
   constexpr int TAPB = NCG * NT * 512;
-  auto bload = [&](int soff, int idx) -> float2 {
-    const int hi = idx >> 2, lo = idx & 3;
-    const u32x2 v = __builtin_amdgcn_raw_buffer_load_b64(rw, lane * 8 + lo * 512, soff + hi * 2048, 0);
-    return make_float2(__uint_as_float(v.x), __uint_as_float(v.y));
-  };
-  const int cpz = KSPLIT ? (ncc + (int)gridDim.z - 1) / (int)gridDim.z : ncc;
-  const int cc_lo = KSPLIT ? (int)blockIdx.z * cpz : 0;
-  const int cc_hi = min(ncc, cc_lo + cpz);
-  const bool psplit = (NTAPS == 8) && mode == 2 && gridDim.z > 1;  // parities over gridDim.z workgroups (atomics)
-  const int npar = (mode == 2) ? 8 / (int)gridDim.z : 1;
-  const int par_lo = (mode == 2) ? (int)blockIdx.z * npar : 0;
-  const int opar = (mode == 1) ? (int)blockIdx.z : 0;
-  const int nit = npar * (cc_hi - cc_lo);
-  float4 stg[NLD];
-  auto halo_loads = [&](int it) {
-    const int ipar = it / (cc_hi - cc_lo) + par_lo;
-    const int cc = cc_lo + (it % (cc_hi - cc_lo));
-    const int pconst =
-        (mode == 2) ? ((((ipar >> 2) & 1) * (D1 * 2) + ((ipar >> 1) & 1)) * (D2 * 2) + (ipar & 1)) * Cin * 4 : 0;
-#pragma unroll
-    for (int hz = 0; hz < HZ; ++hz) {
-      const int gz = z0 - 1 + hz;
-      const bool pv = (unsigned)gz < (unsigned)D0;
-      const int so = (pv ? gz * sZ : 0) + cc * (CK * 4) + pconst;
-#pragma unroll
-      for (int i = 0; i < NJ; ++i) {
-        const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rin, (int)(pv ? vrel[i] : OOB), so, 0);
-        stg[hz * NJ + i] = make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w));
-      }
-    }
-  };
-  if (nit > 0) halo_loads(0);
+  const bool psplit = pit.psplit;  // parities over gridDim.z workgroups (atomics)
+  const int nit = pit.nit;
+  float4 stg[Stager::NLD];
+  if (nit > 0) {
+    const auto first = pit.at(0, D1, D2, Cin);
+    hs.load_all(first.cc, first.pconst, stg);
+  }
   for (int it = 0; it < nit; ++it) {
-    const int ipar = it / (cc_hi - cc_lo);
-    const int cc = cc_lo + it - ipar * (cc_hi - cc_lo);
-    const int par = (mode == 1) ? opar : ipar + par_lo;
-    const int pz = (par >> 2) & 1, py = (par >> 1) & 1, px = par & 1;
-    // position of the 2x2x2 window inside the 3x3x3 stencil: mode 1 shift = parity, mode 2 (flipped taps) 1 - parity
-    const int shz = (NTAPS == 8) ? (mode == 2 ? 1 - pz : pz) : 0, shy = (NTAPS == 8) ? (mode == 2 ? 1 - py : py) : 0,
-              shx = (NTAPS == 8) ? (mode == 2 ? 1 - px : px) : 0;
-    const int shtap = (shz * 3 + shy) * 3 + shx;
-    const int shlds = ((shz * HY + shy) * HX + shx) * CKP;
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < NJ; ++i) {
-      if (i < NJ - 1 || tid + NTHR * i < PL4) {
-#pragma unroll
-        for (int hz = 0; hz < HZ; ++hz) *reinterpret_cast<float4*>(&lds[ldsa[i] + hz * (HY * HX * CKP)]) = stg[hz * NJ + i];
-      }
+    const auto cur = pit.at(it, D1, D2, Cin);
+    const int shlds = ((cur.shz * HY + cur.shy) * HX + cur.shx) * CKP;
+    hs.commit(lds, stg);
+    if (it + 1 < nit) {
+      const auto next = pit.at(it + 1, D1, D2, Cin);
+      hs.load_all(next.cc, next.pconst, stg);
     }
-    __syncthreads();
-    if (it + 1 < nit) halo_loads(it + 1);
 
-    const int wsoff = (int)(((int64_t)(nc * ncc + cc) * 27 + shtap) * TAPB + (int64_t)par * ext.wstride * 4);
+    const int wsoff = pit.wsoff(cur, nc, TAPB);
     int ab[MT];
 #pragma unroll
     for (int m = 0; m < MT; ++m) ab[m] = a_base[m] + shlds;
-    auto tap_id = [](int i) { return NTAPS == 27 ? i : ((i >> 2) & 1) * 9 + ((i >> 1) & 1) * 3 + (i & 1); };
-    auto tap_lds = [&](int i) {
-      const int tt = tap_id(i);
-      return (((tt / 9) * HY + (tt / 3) % 3) * HX + tt % 3) * CKP;
-    };
+    auto tap_id = [](int i) { return ParityIter<KSPLIT, NTAPS>::tap_id(i); };
+    auto tap_lds = [](int i) { return tap_halo_off<HY, HX, CKP>(ParityIter<KSPLIT, NTAPS>::tap_id(i)); };
     float2 bb[2][NCG][NT];
     float2 aa[2][MT];
 #pragma unroll
     for (int g = 0; g < NCG; ++g)
 #pragma unroll
-      for (int n = 0; n < NT; ++n) bb[0][g][n] = bload(wsoff + tap_id(0) * TAPB, g * NT + n);
+      for (int n = 0; n < NT; ++n) bb[0][g][n] = bload(rw, lane, wsoff + tap_id(0) * TAPB, g * NT + n);
 #pragma unroll
     for (int m = 0; m < MT; ++m) aa[0][m] = *reinterpret_cast<const float2*>(&lds[ab[m] + tap_lds(0)]);
 #pragma unroll
@@ -1707,7 +1775,7 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void conv3d_fwd_brick_kernel(const
 #pragma unroll
         for (int g = 0; g < NCG; ++g)
 #pragma unroll
-          for (int n = 0; n < NT; ++n) bb[(ti + 1) & 1][g][n] = bload(wsoff + tap_id(ti + 1) * TAPB, g * NT + n);
+          for (int n = 0; n < NT; ++n) bb[(ti + 1) & 1][g][n] = bload(rw, lane, wsoff + tap_id(ti + 1) * TAPB, g * NT + n);
       }
       const int toff = tap_lds(ti);
       const int toff_n = tap_lds(ti + 1 < NTAPS ? ti + 1 : ti);
@@ -1903,16 +1971,10 @@ __global__ __launch_bounds__(256, 2) void conv3d_wgrad_kernel(const float* __res
     }
     return v;
   };
-  auto tile_origin = [&](int t, int& z0, int& y0, int& x0) {
-    const int t2 = t % tiles2, t1 = (t / tiles2) % tiles1, t0 = t / (tiles2 * tiles1);
-    z0 = t0 * WT0;
-    y0 = t1 * WT1;
-    x0 = t2 * WT2;
-  };
   float4 sx[NX], sd[ND];
   if ((int)blockIdx.x < ntiles) {
     int z0, y0, x0;
-    tile_origin(blockIdx.x, z0, y0, x0);
+    tile_origin<WT1, WT0, WT2>(blockIdx.x, tiles1, tiles2, z0, y0, x0);
 #pragma unroll
     for (int k = 0; k < NX; ++k) sx[k] = load_x(k, z0, y0, x0);
 #pragma unroll
@@ -1954,7 +2016,7 @@ __global__ __launch_bounds__(256, 2) void conv3d_wgrad_kernel(const float* __res
     // while the 32 k-steps below keep the matrix cores busy
     if (t + (int)gridDim.x < ntiles) {
       int z0, y0, x0;
-      tile_origin(t + gridDim.x, z0, y0, x0);
+      tile_origin<WT1, WT0, WT2>(t + gridDim.x, tiles1, tiles2, z0, y0, x0);
 #pragma unroll
       for (int k = 0; k < NX; ++k) sx[k] = load_x(k, z0, y0, x0);
 #pragma unroll
@@ -2114,10 +2176,9 @@ __global__ __launch_bounds__(256, 2) void conv3d_wgrad_lean_kernel(const float* 
 
   const int ntiles = tiles0 * tiles1 * tiles2;
   float4 sx[NX], sd[ND];
-  auto as_f4 = [](u32x4 v) { return make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w)); };
   auto load_tile = [&](int t) {
-    const int t2 = t % tiles2, t1 = (t / tiles2) % tiles1, t0 = t / (tiles2 * tiles1);
-    const int z0 = t0 * WT0, y0 = t1 * WT1, x0 = t2 * WT2;
+    int z0, y0, x0;
+    tile_origin<WT1, WT0, WT2>(t, tiles1, tiles2, z0, y0, x0);
     // x halo
     uint32_t bad = 0x80000000u;
 #pragma unroll
@@ -2318,10 +2379,9 @@ __global__ __launch_bounds__(256, 2) void conv3d_wgrad_box_kernel(const float* _
 
   const int ntiles = tiles0 * tiles1 * tiles2;
   float4 sx[NX], sd[ND];
-  auto as_f4 = [](u32x4 v) { return make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w)); };
   auto load_tile = [&](int t) {
-    const int t2 = t % tiles2, t1 = (t / tiles2) % tiles1, t0 = t / (tiles2 * tiles1);
-    const int z0 = t0 * TZ, y0 = t1 * TY, x0 = t2 * TX;
+    int z0, y0, x0;
+    tile_origin<TY, TZ, TX>(t, tiles1, tiles2, z0, y0, x0);
     uint32_t bad = 0x80000000u;
 #pragma unroll
     for (int h = 0; h < HY; ++h) bad |= ((unsigned)(y0 - 1 + h) >= (unsigned)D1) ? (1u << h) : 0u;
@@ -2446,7 +2506,8 @@ __global__ __launch_bounds__(256, 2) void conv3d_wgrad_c2_kernel(const float* __
                                                                  const float* __restrict__ dout,
                                                                  float* __restrict__ partial, int D0, int D1, int D2,
                                                                  int tiles1, int tiles2, int ntiles) {
-  constexpr int FH1 = 6, FHV = FH0 * FH1 * FH2, NS = (FHV + 255) / 256, Cout = 24, NROW = 27 * CIN;
+  using Stager = HaloStagerVox<CIN>;
+  constexpr int FH1 = Stager::FH1, FHV = Stager::FHV, Cout = 24, NROW = 27 * CIN;
   __shared__ __attribute__((aligned(16))) float lds[2 * FHV * CIN];  // halo tile | ones (read by the dbias lane)
   __shared__ float red[3 * 64 * 24];
   constexpr uint32_t OOB = 0x80000000u;
@@ -2460,28 +2521,17 @@ __global__ __launch_bounds__(256, 2) void conv3d_wgrad_c2_kernel(const float* __
     rbase = (((wave + tap / 9) * FH1 + (tap / 3) % 3) * FH2 + tap % 3) * CIN + ci;
     if (lane == NROW) rbase = FHV * CIN + wave * FH1 * FH2 * CIN;  // ones
   }
-  const __amdgpu_buffer_rsrc_t rin =
-      __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(in), 0, (int)((int64_t)D0 * D1 * D2 * CIN * 4), 0x00020000);
+  const Stager hs(in, D0, D1, D2, tid);
   const __amdgpu_buffer_rsrc_t rdo =
       __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(dout), 0, (int)((int64_t)D0 * D1 * D2 * Cout * 4), 0x00020000);
-  int rel[NS], ldsa[NS];
-  uint32_t cmask[NS];
-#pragma unroll
-  for (int i = 0; i < NS; ++i) {
-    const int j = tid + 256 * i;
-    const int hz = j / (FH1 * FH2), hy = (j / FH2) % FH1, hx = j % FH2;
-    rel[i] = ((hz * D1 + hy) * D2 + hx) * CIN * 4;
-    ldsa[i] = j * CIN;
-    cmask[i] = j < FHV ? ((1u << hz) | (1u << (6 + hy)) | (1u << (12 + hx))) : 0xFFFFFFFFu;
-  }
   int kk[3];  // voxel (0..7) of the octet that register r of this lane belongs to
 #pragma unroll
   for (int r = 0; r < 3; ++r) kk[r] = (64 * r + lane) / 24;
-  float stg[NS][CIN];
+  float stg[Stager::NS][CIN];
   float an[8][3];  // dz of the next tile (this wave's z-plane): 8 octets x 3 registers, requested one tile ahead
   auto load_tile = [&](int t) {
-    const int t2 = t % tiles2, t1 = (t / tiles2) % tiles1, t0 = t / (tiles2 * tiles1);
-    const int z0 = t0 * FT0, y0 = t1 * 4, x0 = t2 * FT2;
+    int z0, y0, x0;
+    tile_origin<4>(t, tiles1, tiles2, z0, y0, x0);
     {
       const int gz = z0 + wave;
 #pragma unroll
@@ -2496,44 +2546,16 @@ __global__ __launch_bounds__(256, 2) void conv3d_wgrad_c2_kernel(const float* __
         }
       }
     }
-    uint32_t bad = 0x80000000u;
-#pragma unroll
-    for (int h = 0; h < FH0; ++h) bad |= ((unsigned)(z0 - 1 + h) >= (unsigned)D0) ? (1u << h) : 0u;
-#pragma unroll
-    for (int h = 0; h < FH1; ++h) bad |= ((unsigned)(y0 - 1 + h) >= (unsigned)D1) ? (1u << (6 + h)) : 0u;
-#pragma unroll
-    for (int h = 0; h < FH2; ++h) bad |= ((unsigned)(x0 - 1 + h) >= (unsigned)D2) ? (1u << (12 + h)) : 0u;
-    const int org = (((z0 - 1) * D1 + (y0 - 1)) * D2 + (x0 - 1)) * CIN * 4;
-#pragma unroll
-    for (int i = 0; i < NS; ++i) {
-      const int vo = (cmask[i] & bad) ? (int)OOB : rel[i] + org;
-      if constexpr (CIN == 2) {
-        const u32x2 v = __builtin_amdgcn_raw_buffer_load_b64(rin, vo, 0, 0);
-        stg[i][0] = __uint_as_float(v.x);
-        stg[i][1] = __uint_as_float(v.y);
-      } else {
-        stg[i][0] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rin, vo, 0, 0));
-      }
-    }
+    hs.load_all(z0, y0, x0, stg);
   };
   f32x4 acc[6];
 #pragma unroll
   for (int g = 0; g < 6; ++g) acc[g] = (f32x4){0.f, 0.f, 0.f, 0.f};
   const int G = gridDim.x;
-  const int my_pos = (blockIdx.x & 7) * (G >> 3) + (blockIdx.x >> 3);
+  const int my_pos = xcd_start_pos();
   if (my_pos < ntiles) load_tile(my_pos);
   for (int t = my_pos; t < ntiles; t += G) {
-    const int t2 = t % tiles2, t1 = (t / tiles2) % tiles1, t0 = t / (tiles2 * tiles1);
-    const int z0 = t0 * FT0, y0 = t1 * 4, x0 = t2 * FT2;
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < NS; ++i) {
-      if (i < NS - 1 || tid + 256 * i < FHV) {
-#pragma unroll
-        for (int c = 0; c < CIN; ++c) lds[ldsa[i] + c] = stg[i][c];
-      }
-    }
-    __syncthreads();
+    hs.commit(lds, stg);
     float ar[8][3];
 #pragma unroll
     for (int o = 0; o < 8; ++o)
@@ -2615,14 +2637,14 @@ __global__ __launch_bounds__(256, 2) void conv3d_up_wgrad_p4_kernel(const float*
                                                                     int64_t dwstride, int64_t det_stride) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   constexpr int CK = 24, MT = 4, Cout = 24;
-  constexpr int FT1 = MT, FH1 = MT + 2, CKP = CK + 4, C4 = CK / 4, NQ = 3;
+  constexpr int FT1 = MT, FH1 = MT + 2, CKP = CK + 4, NQ = 3;
   constexpr uint32_t OOB = 0x80000000u;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int par = (blockIdx.y & 1) * 4 + wave, cc = blockIdx.y >> 1;
   const int pz = (par >> 2) & 1, py = (par >> 1) & 1, px = par & 1;
   const int G = gridDim.x;
-  const int my_pos = (blockIdx.x & 7) * (G >> 3) + (blockIdx.x >> 3);
+  const int my_pos = xcd_start_pos();
 
   // B rows of this lane: block = 16 q + (lane >> 2) = window tap * 6 + quad
   int rowoff[NQ];
@@ -2633,22 +2655,10 @@ __global__ __launch_bounds__(256, 2) void conv3d_up_wgrad_p4_kernel(const float*
     const int tz = pz + ((ti >> 2) & 1), ty = py + ((ti >> 1) & 1), tx = px + (ti & 1);
     rowoff[q] = ((tz * FH1 + ty) * FH2 + tx) * CKP + quad * 4 + (lane & 3);
   }
-  constexpr int PLANE4 = FH1 * FH2 * C4, NJ = (PLANE4 + 255) / 256, NLD = NJ * FH0;
-  const __amdgpu_buffer_rsrc_t rin =
-      __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(in), 0, (int)((int64_t)D0 * D1 * D2 * Cin * 4), 0x00020000);
+  using Stager = HaloStagerWalk<FH1, CK>;
+  const Stager hs(in, D0, D1, D2, Cin, tid);
   const __amdgpu_buffer_rsrc_t rdo = __builtin_amdgcn_make_buffer_rsrc(
       const_cast<float*>(dout), 0, (int)((int64_t)D0 * D1 * D2 * 8 * Cout * 4), 0x00020000);
-  int rel[NJ], ldsa[NJ];
-  uint32_t cmask[NJ];
-#pragma unroll
-  for (int i = 0; i < NJ; ++i) {
-    const int j = tid + 256 * i;
-    const int hy = j / (FH2 * C4), r = j - hy * (FH2 * C4), hx = r / C4, c4 = r - hx * C4;
-    rel[i] = ((hy * D2 + hx) * Cin + c4 * 4) * 4;
-    ldsa[i] = ((hy * FH2 + hx) * CKP + c4 * 4);
-    cmask[i] = j < PLANE4 ? ((1u << hy) | (1u << (8 + hx))) : 0xFFFFFFFFu;
-  }
-  const int plane_bytes = D1 * D2 * Cin * 4;
   int kk[3], aoff[3];  // dz register r, lane l <-> float 64 r + l = 24 k + c of an octet; voxel stride 2 in the hi-res row
 #pragma unroll
   for (int r = 0; r < 3; ++r) {
@@ -2656,35 +2666,11 @@ __global__ __launch_bounds__(256, 2) void conv3d_up_wgrad_p4_kernel(const float*
     kk[r] = f / 24;
     aoff[r] = (kk[r] * 2 * Cout + (f - kk[r] * 24)) * 4;
   }
-  float4 stg[NLD];
-  auto tile_origin = [&](int t, int& z0, int& y0, int& x0) {
-    const int t2 = t % tiles2, t1 = (t / tiles2) % tiles1, t0 = t / (tiles2 * tiles1);
-    z0 = t0 * FT0;
-    y0 = t1 * FT1;
-    x0 = t2 * FT2;
-  };
+  float4 stg[Stager::NLD];
   auto load_halo = [&](int t) {
     int z0, y0, x0;
-    tile_origin(t, z0, y0, x0);
-    uint32_t bad = 0x80000000u;
-#pragma unroll
-    for (int h = 0; h < FH1; ++h) bad |= ((unsigned)(y0 - 1 + h) >= (unsigned)D1) ? (1u << h) : 0u;
-#pragma unroll
-    for (int h = 0; h < FH2; ++h) bad |= ((unsigned)(x0 - 1 + h) >= (unsigned)D2) ? (1u << (8 + h)) : 0u;
-    const int yx = (((y0 - 1) * D2 + (x0 - 1)) * Cin + cc * CK) * 4;
-    uint32_t voff[NJ];
-#pragma unroll
-    for (int i = 0; i < NJ; ++i) voff[i] = (cmask[i] & bad) ? OOB : (uint32_t)(rel[i] + yx);
-#pragma unroll
-    for (int hz = 0; hz < FH0; ++hz) {
-      const int gz = z0 - 1 + hz;
-      const bool pv = (unsigned)gz < (unsigned)D0;
-#pragma unroll
-      for (int i = 0; i < NJ; ++i) {
-        const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rin, (int)(pv ? voff[i] : OOB), pv ? gz * plane_bytes : 0, 0);
-        stg[hz * NJ + i] = make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w));
-      }
-    }
+    tile_origin<FT1>(t, tiles1, tiles2, z0, y0, x0);
+    hs.load_all(z0, y0, x0, cc, stg);
   };
   // dz of z-plane `z` of tile (z0, y0, x0) on this wave's parity: 8 octets (row y = o >> 1, x half o & 1) x 3 registers
   auto load_dz = [&](int z0, int y0, int x0, int z, float (&a)[8][3]) {
@@ -2711,24 +2697,15 @@ __global__ __launch_bounds__(256, 2) void conv3d_up_wgrad_p4_kernel(const float*
   int z0 = 0, y0 = 0, x0 = 0;
   if (my_pos < ntiles) {
     load_halo(my_pos);
-    tile_origin(my_pos, z0, y0, x0);
+    tile_origin<FT1>(my_pos, tiles1, tiles2, z0, y0, x0);
     load_dz(z0, y0, x0, 0, an);
   }
   for (int t = my_pos; t < ntiles; t += G) {
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < NJ; ++i) {
-      if (i < NJ - 1 || tid + 256 * i < PLANE4) {
-#pragma unroll
-        for (int hz = 0; hz < FH0; ++hz)
-          *reinterpret_cast<float4*>(&lds[ldsa[i] + hz * (FH1 * FH2 * CKP)]) = stg[hz * NJ + i];
-      }
-    }
-    __syncthreads();
+    hs.commit(lds, stg);
     const bool has_next = t + G < ntiles;
     if (has_next) load_halo(t + G);
     int nz0 = z0, ny0 = y0, nx0 = x0;
-    if (has_next) tile_origin(t + G, nz0, ny0, nx0);
+    if (has_next) tile_origin<FT1>(t + G, tiles1, tiles2, nz0, ny0, nx0);
     for (int z = 0; z < FT0; ++z) {
       float ar[8][3];
 #pragma unroll
@@ -3051,6 +3028,27 @@ inline int splitk_end(float* out, const float* bias, int64_t nout, int Cout, int
   return hipGetLastError() == hipSuccess ? SYNTHSR_OK : SYNTHSR_ELAUNCH;
 }
 
+// launch geometry of the persistent kernels: 4 x ft1 x 16 tiles and the LDS bytes of their 6 x (ft1 + 2) x 18 x (24 + 4) halo tile
+struct PersistGeom {
+  int tiles0, tiles1, tiles2, ntiles;
+  size_t smem;
+};
+inline PersistGeom persist_geometry(const int s[3], int ft1 = 4) {
+  PersistGeom g;
+  g.tiles0 = cdiv(s[0], FT0);
+  g.tiles1 = cdiv(s[1], ft1);
+  g.tiles2 = cdiv(s[2], FT2);
+  g.ntiles = g.tiles0 * g.tiles1 * g.tiles2;
+  g.smem = (size_t)FH0 * (ft1 + 2) * FH2 * 28 * sizeof(float);
+  return g;
+}
+// workgroups along x: `cap` (a multiple of 8, one share per XCD: xcd_start_pos), less where there are fewer items to walk
+inline int persist_grid_x(int cap, int64_t nitems) {
+  int gx = cap;
+  while (gx > 8 && gx > nitems) gx -= 8;
+  return gx;
+}
+
 template <int CK, int NT, int MT, bool KS>
 int launch_fwd(const float* in, const float* wp, const float* bias, float* out, const int s[3], int Cin, int Cout,
                const FwdPlan& pl, int act, hipStream_t st, const ConvExt& ext) {
@@ -3096,35 +3094,28 @@ template <int NT>
 int launch_fwd_persist(const float* in, const float* wp, const float* bias, float* out, const int s[3], int Cin, int Cout,
                        const FwdPlan& pl, int act, hipStream_t st, const float* addend) {
   const bool relu = launch_act(act);
-  const int tiles0 = cdiv(s[0], FT0), tiles1 = cdiv(s[1], 4), tiles2 = cdiv(s[2], FT2);
-  const int ntiles = tiles0 * tiles1 * tiles2;
-  const size_t smem = (size_t)FH0 * 6 * FH2 * 28 * sizeof(float);
-  int gx = 512 / pl.nchunks;  // 2 workgroups per CU in total
-  gx = std::max(8, (gx / 8) * 8);
-  const int64_t nitems = (int64_t)ntiles * pl.ncc;
-  while (gx > 8 && gx > nitems) gx -= 8;
+  const PersistGeom g = persist_geometry(s);
+  // 2 workgroups per CU in total
+  const int gx = persist_grid_x(std::max(8, (512 / pl.nchunks / 8) * 8), (int64_t)g.ntiles * pl.ncc);
   launch_smem<conv3d_fwd_persist_kernel<NT>, conv3d_fwd_persist_kernel<NT, true>>(
-      relu, dim3(gx, pl.nchunks), dim3(256), smem, st, in, wp, bias, out, s[0], s[1], s[2], Cin, Cout, pl.ncc, tiles1, tiles2,
-      ntiles, act, addend);
+      relu, dim3(gx, pl.nchunks), dim3(256), g.smem, st, in, wp, bias, out, s[0], s[1], s[2], Cin, Cout, pl.ncc, g.tiles1,
+      g.tiles2, g.ntiles, act, addend);
   return hipGetLastError() == hipSuccess ? SYNTHSR_OK : SYNTHSR_ELAUNCH;
 }
 
 int launch_fwd_p4(const float* in, const float* wp, const float* bias, float* out, const int s[3], int Cin,
                   const FwdPlan& pl, int act, hipStream_t st, const float* addend, float* stats = nullptr) {
   const bool relu = launch_act(act);
-  const int tiles0 = cdiv(s[0], FT0), tiles1 = cdiv(s[1], 4), tiles2 = cdiv(s[2], FT2);
-  const int ntiles = tiles0 * tiles1 * tiles2;
-  const size_t smem = (size_t)FH0 * 6 * FH2 * 28 * sizeof(float);
-  int gx = 512;
-  while (gx > 8 && gx > ntiles) gx -= 8;
+  const PersistGeom g = persist_geometry(s);
+  const int gx = persist_grid_x(512, g.ntiles);
   float* partial = nullptr;
   if (stats) {  // BatchNorm statistics of the output: per-workgroup partials in library scratch, then a tiny reduction
     partial = ctx_scratch((size_t)gx * 48 * sizeof(float));
     if (!partial) return SYNTHSR_EWORKSPACE;
   }
-  launch_smem<conv3d_fwd_p4_kernel<false>, conv3d_fwd_p4_kernel<true>>(relu, dim3(gx), dim3(256), smem, st, in, wp, bias, out,
-                                                                       s[0], s[1], s[2], Cin, pl.ncc, tiles1, tiles2, ntiles,
-                                                                       act, addend, partial);
+  launch_smem<conv3d_fwd_p4_kernel<false>, conv3d_fwd_p4_kernel<true>>(relu, dim3(gx), dim3(256), g.smem, st, in, wp, bias, out,
+                                                                       s[0], s[1], s[2], Cin, pl.ncc, g.tiles1, g.tiles2,
+                                                                       g.ntiles, act, addend, partial);
   if (hipGetLastError() != hipSuccess) return SYNTHSR_ELAUNCH;
   if (stats) return synthsr_bn_stats_from_partials(partial, gx, (int64_t)s[0] * s[1] * s[2], 24, stats, st);
   return SYNTHSR_OK;
@@ -3180,27 +3171,22 @@ int dispatch_fwd_brick(const float* in, const float* wp, const float* bias, floa
 int launch_fwd_c2(const float* in, const float* wp, const float* bias, float* out, const int s[3], int Cin, int act,
                   hipStream_t st) {
   const bool relu = launch_act(act);
-  const int tiles0 = cdiv(s[0], FT0), tiles1 = cdiv(s[1], 4), tiles2 = cdiv(s[2], FT2);
-  const int ntiles = tiles0 * tiles1 * tiles2;
-  int gx = 2048;  // 8 workgroups per CU: the kernel is bound by its output stores, not by the matrix cores
-  while (gx > 8 && gx > ntiles) gx -= 8;
+  const PersistGeom g = persist_geometry(s);  // the tile counts only: this kernel's LDS is static
+  const int gx = persist_grid_x(2048, g.ntiles);  // 8 workgroups per CU: bound by its output stores, not by the matrix cores
   auto kern = Cin == 2 ? (relu ? conv3d_fwd_c2_kernel<2, true> : conv3d_fwd_c2_kernel<2, false>)
                         : (relu ? conv3d_fwd_c2_kernel<1, true> : conv3d_fwd_c2_kernel<1, false>);
-  hipLaunchKernelGGL(kern, dim3(gx), dim3(256), 0, st, in, wp, bias, out, s[0], s[1], s[2], tiles1, tiles2, ntiles, act);
+  hipLaunchKernelGGL(kern, dim3(gx), dim3(256), 0, st, in, wp, bias, out, s[0], s[1], s[2], g.tiles1, g.tiles2, g.ntiles, act);
   return hipGetLastError() == hipSuccess ? SYNTHSR_OK : SYNTHSR_ELAUNCH;
 }
 
 int launch_up_fwd_p4(const float* in, const float* wp, const float* bias, float* out, const int s[3], int Cin,
                      const FwdPlan& pl, int act, hipStream_t st, int64_t wstride, const float* addend) {
   const bool relu = launch_act(act);
-  const int tiles0 = cdiv(s[0], FT0), tiles1 = cdiv(s[1], 4), tiles2 = cdiv(s[2], FT2);
-  const int ntiles = tiles0 * tiles1 * tiles2;
-  const size_t smem = (size_t)FH0 * 6 * FH2 * 28 * sizeof(float);
-  int gx = 512;
-  while (gx > 8 && gx > ntiles) gx -= 8;
-  launch_smem<conv3d_up_fwd_p4_kernel<false>, conv3d_up_fwd_p4_kernel<true>>(relu, dim3(gx), dim3(256), smem, st, in, wp, bias,
-                                                                             out, s[0], s[1], s[2], Cin, pl.ncc, tiles1, tiles2,
-                                                                             ntiles, act, wstride, addend);
+  const PersistGeom g = persist_geometry(s);
+  const int gx = persist_grid_x(512, g.ntiles);
+  launch_smem<conv3d_up_fwd_p4_kernel<false>, conv3d_up_fwd_p4_kernel<true>>(relu, dim3(gx), dim3(256), g.smem, st, in, wp, bias,
+                                                                             out, s[0], s[1], s[2], Cin, pl.ncc, g.tiles1,
+                                                                             g.tiles2, g.ntiles, act, wstride, addend);
   return hipGetLastError() == hipSuccess ? SYNTHSR_OK : SYNTHSR_ELAUNCH;
 }
 
@@ -3402,13 +3388,13 @@ __global__ __launch_bounds__(256, 2) void conv3d_wgrad_p4_kernel(const float* __
                                                                  float* __restrict__ dbias, int64_t det_stride) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   constexpr int CK = 24, MT = 4, Cout = 24;
-  constexpr int FT1 = MT, FH1 = MT + 2, CKP = CK + 4, C4 = CK / 4;
+  constexpr int FT1 = MT, FH1 = MT + 2, CKP = CK + 4;
   constexpr int NBLK = 27 * 6, BPW = (NBLK + 3) / 4, NQ = (BPW + 15) / 16;  // 41 blocks per wave in 3 registers
   constexpr uint32_t OOB = 0x80000000u;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int cc = blockIdx.y;
   const int G = gridDim.x;
-  const int my_pos = (blockIdx.x & 7) * (G >> 3) + (blockIdx.x >> 3);
+  const int my_pos = xcd_start_pos();
 
   // B rows of this lane: block blk = wave*BPW + 16 q + (lane >> 2), channel 4*quad + (lane & 3)
   int rowoff[NQ];
@@ -3429,55 +3415,19 @@ __global__ __launch_bounds__(256, 2) void conv3d_wgrad_p4_kernel(const float* __
   for (int v = tid; v < FH0 * FH1 * FH2; v += 256)
     *reinterpret_cast<float4*>(&lds[v * CKP + CK]) = make_float4(1.f, 0.f, 0.f, 0.f);
 
-  // ---- x halo staging (as conv3d_fwd_p4_kernel)
-  constexpr int PLANE4 = FH1 * FH2 * C4, NJ = (PLANE4 + 255) / 256, NLD = NJ * FH0;
-  const __amdgpu_buffer_rsrc_t rin =
-      __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(in), 0, (int)((int64_t)D0 * D1 * D2 * Cin * 4), 0x00020000);
+  // ---- x halo staging
+  using Stager = HaloStagerWalk<FH1, CK>;
+  const Stager hs(in, D0, D1, D2, Cin, tid);
   const __amdgpu_buffer_rsrc_t rdo =
       __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(dout), 0, (int)((int64_t)D0 * D1 * D2 * Cout * 4), 0x00020000);
-  int rel[NJ], ldsa[NJ];
-  uint32_t cmask[NJ];
-#pragma unroll
-  for (int i = 0; i < NJ; ++i) {
-    const int j = tid + 256 * i;
-    const int hy = j / (FH2 * C4), r = j - hy * (FH2 * C4), hx = r / C4, c4 = r - hx * C4;
-    rel[i] = ((hy * D2 + hx) * Cin + c4 * 4) * 4;
-    ldsa[i] = ((hy * FH2 + hx) * CKP + c4 * 4);
-    cmask[i] = j < PLANE4 ? ((1u << hy) | (1u << (8 + hx))) : 0xFFFFFFFFu;
-  }
-  const int plane_bytes = D1 * D2 * Cin * 4;
   int kk[3];  // voxel (0..7) of the octet that dz register r of this lane belongs to
 #pragma unroll
   for (int r = 0; r < 3; ++r) kk[r] = (64 * r + lane) / 24;
-  float4 stg[NLD];
-  auto tile_origin = [&](int t, int& z0, int& y0, int& x0) {
-    const int t2 = t % tiles2, t1 = (t / tiles2) % tiles1, t0 = t / (tiles2 * tiles1);
-    z0 = t0 * FT0;
-    y0 = t1 * FT1;
-    x0 = t2 * FT2;
-  };
+  float4 stg[Stager::NLD];
   auto load_halo = [&](int t) {
     int z0, y0, x0;
-    tile_origin(t, z0, y0, x0);
-    uint32_t bad = 0x80000000u;
-#pragma unroll
-    for (int h = 0; h < FH1; ++h) bad |= ((unsigned)(y0 - 1 + h) >= (unsigned)D1) ? (1u << h) : 0u;
-#pragma unroll
-    for (int h = 0; h < FH2; ++h) bad |= ((unsigned)(x0 - 1 + h) >= (unsigned)D2) ? (1u << (8 + h)) : 0u;
-    const int yx = (((y0 - 1) * D2 + (x0 - 1)) * Cin + cc * CK) * 4;
-    uint32_t voff[NJ];
-#pragma unroll
-    for (int i = 0; i < NJ; ++i) voff[i] = (cmask[i] & bad) ? OOB : (uint32_t)(rel[i] + yx);
-#pragma unroll
-    for (int hz = 0; hz < FH0; ++hz) {
-      const int gz = z0 - 1 + hz;
-      const bool pv = (unsigned)gz < (unsigned)D0;
-#pragma unroll
-      for (int i = 0; i < NJ; ++i) {
-        const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rin, (int)(pv ? voff[i] : OOB), pv ? gz * plane_bytes : 0, 0);
-        stg[hz * NJ + i] = make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w));
-      }
-    }
+    tile_origin<FT1>(t, tiles1, tiles2, z0, y0, x0);
+    hs.load_all(z0, y0, x0, cc, stg);
   };
   // dz of z-plane `z` of tile (z0, y0, x0): 8 octets (row y = o >> 1, x half o & 1) x 3 registers
   auto load_dz = [&](int z0, int y0, int x0, int z, float (&a)[8][3]) {
@@ -3504,24 +3454,15 @@ __global__ __launch_bounds__(256, 2) void conv3d_wgrad_p4_kernel(const float* __
   int z0 = 0, y0 = 0, x0 = 0;
   if (my_pos < ntiles) {
     load_halo(my_pos);
-    tile_origin(my_pos, z0, y0, x0);
+    tile_origin<FT1>(my_pos, tiles1, tiles2, z0, y0, x0);
     load_dz(z0, y0, x0, 0, an);
   }
   for (int t = my_pos; t < ntiles; t += G) {
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < NJ; ++i) {
-      if (i < NJ - 1 || tid + 256 * i < PLANE4) {
-#pragma unroll
-        for (int hz = 0; hz < FH0; ++hz)
-          *reinterpret_cast<float4*>(&lds[ldsa[i] + hz * (FH1 * FH2 * CKP)]) = stg[hz * NJ + i];
-      }
-    }
-    __syncthreads();
+    hs.commit(lds, stg);
     const bool has_next = t + G < ntiles;
     if (has_next) load_halo(t + G);
     int nz0 = z0, ny0 = y0, nx0 = x0;
-    if (has_next) tile_origin(t + G, nz0, ny0, nx0);
+    if (has_next) tile_origin<FT1>(t + G, tiles1, tiles2, nz0, ny0, nx0);
     for (int z = 0; z < FT0; ++z) {
       float ar[8][3];
 #pragma unroll
@@ -3582,18 +3523,16 @@ __global__ __launch_bounds__(256, 2) void conv3d_wgrad_p4_kernel(const float* __
 
 int launch_wgrad_c2(const float* in, const float* dout, float* dw, float* dbias, const int s[3], int Cin, hipStream_t st,
                     const WgExt& ext) {
-  const int tiles0 = cdiv(s[0], FT0), tiles1 = cdiv(s[1], 4), tiles2 = cdiv(s[2], FT2);
-  const int ntiles = tiles0 * tiles1 * tiles2;
-  int gx = 2048;  // 8 per CU: per-tile work is short, latency is hidden by occupancy
-  while (gx > 8 && gx > ntiles) gx -= 8;
+  const PersistGeom g = persist_geometry(s);  // the tile counts only: this kernel's LDS is static
+  const int gx = persist_grid_x(2048, g.ntiles);  // 8 per CU: per-tile work is short, latency is hidden by occupancy
   float* partial = ctx_scratch((size_t)gx * 1536 * sizeof(float));
   if (!partial) return SYNTHSR_EWORKSPACE;
   if (Cin == 2)
-    hipLaunchKernelGGL(conv3d_wgrad_c2_kernel<2>, dim3(gx), dim3(256), 0, st, in, dout, partial, s[0], s[1], s[2], tiles1,
-                       tiles2, ntiles);
+    hipLaunchKernelGGL(conv3d_wgrad_c2_kernel<2>, dim3(gx), dim3(256), 0, st, in, dout, partial, s[0], s[1], s[2], g.tiles1,
+                       g.tiles2, g.ntiles);
   else
-    hipLaunchKernelGGL(conv3d_wgrad_c2_kernel<1>, dim3(gx), dim3(256), 0, st, in, dout, partial, s[0], s[1], s[2], tiles1,
-                       tiles2, ntiles);
+    hipLaunchKernelGGL(conv3d_wgrad_c2_kernel<1>, dim3(gx), dim3(256), 0, st, in, dout, partial, s[0], s[1], s[2], g.tiles1,
+                       g.tiles2, g.ntiles);
   if (hipGetLastError() != hipSuccess) return SYNTHSR_ELAUNCH;
   const int nrow = 27 * Cin;
   hipLaunchKernelGGL(rows_reduce_kernel, dim3(cdiv((nrow + 1) * 24, 64), 32), dim3(64), 0, st, partial, gx, dw, dbias, nrow,
@@ -3611,18 +3550,17 @@ int dispatch_wgrad(const float* in, const float* dout, float* dw, const int shap
       if (rc != SYNTHSR_EINVAL) return rc;
     }
     const int64_t vox = (int64_t)shape[0] * shape[1] * shape[2];
-    const int tiles0 = cdiv(shape[0], FT0), tiles1 = cdiv(shape[1], 4), tiles2 = cdiv(shape[2], FT2);
-    const int ntiles = tiles0 * tiles1 * tiles2, ncc = Cin / 24;
-    if (Cout == 24 && (Cin % 24) == 0 && ntiles >= 768 && vox * Cin * 4 < (1ll << 31) && vox * 8 * Cout * 4 < (1ll << 31)) {
-      const size_t smem = (size_t)FH0 * 6 * FH2 * 28 * sizeof(float);
-      max_dyn_smem<conv3d_up_wgrad_p4_kernel>(smem);
-      int gx = std::max(8, ((512 / (ncc * 2)) / 8) * 8);  // each workgroup carries 4 of the 8 parities (one per wave)
-      while (gx > 8 && gx > ntiles) gx -= 8;
+    const PersistGeom g = persist_geometry(shape);
+    const int ncc = Cin / 24;
+    if (Cout == 24 && (Cin % 24) == 0 && g.ntiles >= 768 && vox * Cin * 4 < (1ll << 31) && vox * 8 * Cout * 4 < (1ll << 31)) {
+      max_dyn_smem<conv3d_up_wgrad_p4_kernel>(g.smem);
+      // each workgroup carries 4 of the 8 parities (one per wave)
+      const int gx = persist_grid_x(std::max(8, ((512 / (ncc * 2)) / 8) * 8), g.ntiles);
       DetRun det;
       float* no_dbias = nullptr;
       if (const int rc_ = syn_det_prepare(&det, &dw, &no_dbias, 8 * ext.dwstride, Cout, gx, st)) return rc_;
-      hipLaunchKernelGGL(conv3d_up_wgrad_p4_kernel, dim3(gx, ncc * 2), dim3(256), smem, st, in, dout, dw, shape[0], shape[1],
-                         shape[2], Cin, tiles1, tiles2, ntiles, ext.dwstride, det.stride);
+      hipLaunchKernelGGL(conv3d_up_wgrad_p4_kernel, dim3(gx, ncc * 2), dim3(256), g.smem, st, in, dout, dw, shape[0], shape[1],
+                         shape[2], Cin, g.tiles1, g.tiles2, g.ntiles, ext.dwstride, det.stride);
       if (hipGetLastError() != hipSuccess) return SYNTHSR_ELAUNCH;
       return syn_det_finish(&det, st);
     }
@@ -3639,17 +3577,15 @@ int dispatch_wgrad(const float* in, const float* dout, float* dw, const int shap
   if constexpr (NTAPS == 27) {
     const int64_t vox = (int64_t)shape[0] * shape[1] * shape[2];
     if (Cout == 24 && (Cin % 24) == 0 && vox * Cin * 4 < (1ll << 31) && vox * Cout * 4 < (1ll << 31)) {
-      const int tiles0 = cdiv(shape[0], FT0), tiles1 = cdiv(shape[1], 4), tiles2 = cdiv(shape[2], FT2);
-      const int ntiles = tiles0 * tiles1 * tiles2, ncc = Cin / 24;
-      const size_t smem = (size_t)FH0 * 6 * FH2 * 28 * sizeof(float);
-      max_dyn_smem<conv3d_wgrad_p4_kernel>(smem);
-      int gx = std::max(8, ((512 / ncc) / 8) * 8);
-      while (gx > 8 && gx > ntiles) gx -= 8;
+      const PersistGeom g = persist_geometry(shape);
+      const int ncc = Cin / 24;
+      max_dyn_smem<conv3d_wgrad_p4_kernel>(g.smem);
+      const int gx = persist_grid_x(std::max(8, ((512 / ncc) / 8) * 8), g.ntiles);
       DetRun det;
       float* dbias = ext.dbias;
       if (const int rc_ = syn_det_prepare(&det, &dw, &dbias, (int64_t)27 * ext.cin_total * Cout, Cout, gx, st)) return rc_;
-      hipLaunchKernelGGL(conv3d_wgrad_p4_kernel, dim3(gx, ncc), dim3(256), smem, st, in, dout, dw, shape[0], shape[1],
-                         shape[2], Cin, tiles1, tiles2, ntiles, ext.cin_total, ext.ci_off, dbias, det.stride);
+      hipLaunchKernelGGL(conv3d_wgrad_p4_kernel, dim3(gx, ncc), dim3(256), g.smem, st, in, dout, dw, shape[0], shape[1],
+                         shape[2], Cin, g.tiles1, g.tiles2, g.ntiles, ext.cin_total, ext.ci_off, dbias, det.stride);
       if (hipGetLastError() != hipSuccess) return SYNTHSR_ELAUNCH;
       return syn_det_finish(&det, st);
     }

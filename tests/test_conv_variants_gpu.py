@@ -105,6 +105,7 @@ CASES = [
     # ---- fp32 matrix instructions, plain 27-tap conv
     _c('c2_cin1', 'plain', 'fp32_mfma', 'f32', (6, 5, 17), 1, 24, 'c2_cin1'),
     _c('c2_cin2', 'plain', 'fp32_mfma', 'f32', (6, 5, 17), 2, 24, 'c2_cin2'),
+    _c('c2_cin2_below_tile', 'plain', 'fp32_mfma', 'f32', (3, 5, 7), 2, 24, 'c2_cin2'),   # z and x extents below the 4 x 4 x 16 tile
     _c('p4', 'plain', 'fp32_mfma', 'f32', T768, 24, 24, 'p4'),
     _c('persist_nt1', 'plain', 'fp32_mfma', 'f32', T768, 24, 16, 'persist_nt1'),
     _c('persist_nt2_cout20', 'plain', 'fp32_mfma', 'f32', T768, 24, 20, 'persist_nt2'),

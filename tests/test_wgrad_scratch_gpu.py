@@ -51,7 +51,9 @@ CASES = [
     _c('box_x8', 'plain', 'fp32_mfma', 'f32', (4, 8, 8), 48, 96, 'box_x8'),
     _c('box_x4', 'plain', 'fp32_mfma', 'f32', (4, 4, 12), 48, 96, 'box_x4'),
     _c('p4', 'plain', 'fp32_mfma', 'f32', (5, 6, 18), 48, 24, 'p4'),
+    _c('p4_below_tile', 'plain', 'fp32_mfma', 'f32', (3, 5, 7), 24, 24, 'p4'),   # z and x extents below the 4 x 4 x 16 tile
     _c('c2_cin2', 'plain', 'fp32_mfma', 'f32', (6, 5, 17), 2, 24, 'c2', planes=False),
+    _c('c2_cin2_below_tile', 'plain', 'fp32_mfma', 'f32', (3, 5, 7), 2, 24, 'c2', planes=False),
     _c('c2_cin1', 'plain', 'fp32_mfma', 'f32', (6, 5, 17), 1, 24, 'c2', planes=False),
     # ... split arithmetic (conv_split.hip: 8 / 24 / 16 input channels per workgroup), and a layer it hands back
     _c('split_8x24', 'plain', 'split', 'f32', (6, 6, 6), 8, 24, 'split', split=True),
