@@ -713,6 +713,27 @@ int synthsr_seg_keep_largest(const int32_t* labels, const int32_t* comp, const i
                              int32_t fill_value, int32_t* out, int64_t* stats, void* workspace, int64_t workspace_bytes,
                              synthsr_stream_t stream);
 
+/* --- a label map on another voxel grid, from the posteriors: interpolate, then argmax ---------------------------------------
+ * probs [src_shape[0]][src_shape[1]][src_shape[2]][N] fp32 posteriors, channel last (what synthsr_seg_head_fwd and the
+ * probs_out of synthsr_seg_head_tta_argmax write, bf16 networks included); box [6] = lo0 lo1 lo2 hi0 hi1 hi2, inclusive: the part
+ * of the source that holds the volume; M [12], row-major 3 x 4 on the host: output voxel index (i, j, k, 1) -> source voxel
+ * coordinates; labels [N]: channel -> label VALUE.  out [out_shape[0]][out_shape[1]][out_shape[2]] int32, every element written.
+ *   coordinates  pos[a] = M[a][0] i + M[a][1] j + M[a][2] k + M[a][3], evaluated in double on the device.
+ *   inside       a voxel is inside when lo[a] - 0.5 <= pos[a] <= hi[a] + 0.5 on all three axes; its position is then clamped to
+ *                [lo[a], hi[a]].  An outside voxel gets out = fill_value and, if asked for, probs_out = 0 in every channel.
+ *   corners      i0 = min(floor(pos), max(hi - 1, lo)), i1 = min(i0 + 1, hi), w = pos - i0 rounded to fp32 (the rules of
+ *                volumes.resample_volume_like); an axis whose box is one voxel thick has i0 = i1 = lo and w = 0.
+ *   interpolate  p[n] = sum over the eight corners of wz wy wx probs[corner][n] in fp32, the weight of a corner the product of
+ *                w (the corner at i1) or 1 - w (at i0) per axis.  Nothing outside the box is read.
+ *   label        out = labels[argmax_n p[n]]; on exactly equal values the lowest channel wins (synthsr_seg_head_argmax's rule).
+ *   probs_out    NULL, or [nvox_out][N]: p[n].  It may not overlap probs.
+ * Limits: every source and output side 1 .. 1024, 2 <= N <= 64, 0 <= lo <= hi < the source side.  A NULL required pointer, a
+ * non-finite entry of M or anything outside these limits returns SYNTHSR_EINVAL before any launch.  One launch; the library
+ * allocates nothing and needs no workspace. */
+int synthsr_seg_resample_argmax(const float* probs, const int* src_shape, int N, const int* box, const double* M,
+                                const int* out_shape, const int32_t* labels, int32_t fill_value, int32_t* out, float* probs_out,
+                                synthsr_stream_t stream);
+
 /* --- a frozen or inference softmax-headed U-Net in bf16 ------------------------------------------------------------------
  * The feature map x [nvox][C] is bf16 (8-byte aligned: one channel quad per vector load); BatchNorm statistics, gamma / beta,
  * the head's fp32 master weights w / b, posteriors, prev and the Dice sums stay fp32, so the arithmetic on a given bf16 x is

@@ -7,7 +7,7 @@ the result with the per-label Dice coefficient and the distances between the sur
                                            [--n_levels 5 --conv_per_level 2 --unet_feat 24 --feat_mult 2 --activation elu]
                                            [--dtype f32|bf16]
                                            [--keep_largest per_label|foreground|G.npy [--connectivity 6|18|26] [--fill_label V]]
-                                           [--volumes V.npy|V.csv]
+                                           [--volumes V.npy|V.csv] [--native_space]
                                            [--truth <path> [--scores S.npy|S.csv]
                                                             [--surface_scores D.npy|D.csv [--surface_percentile 95]]]
 
@@ -20,7 +20,12 @@ at 1 mm): .npy [n_volumes, 3, N] in that order; .csv a header of label values, t
 --keep_largest: write only the largest connected component of every group of labels (per_label: every label but the fill label
 is a group; foreground: they form one group; G.npy: a group id per head channel, -1 = untouched), under --connectivity; the
 removed voxels become --fill_label (default: the first label of --labels).  Dice and surface scores are then those of the
-filtered maps.  --volumes: the volume of every label in every written map, in mm^3: .npy [n_volumes, N]; .csv as --scores."""
+filtered maps.  --volumes: the volume of every label in every written map, in mm^3: .npy [n_volumes, N]; .csv as --scores.
+--native_space: label maps (and --posteriors) are written on each image's own voxel grid, with its shape and affine, instead of
+the 1 mm RAS frame: the 1 mm posteriors are interpolated onto that grid and the argmax is taken there.  --truth label maps are
+then expected on each image's own grid, --volumes counts voxels of the image's own volume |det(affine[:3, :3])|, and
+--surface_scores measures in the image's voxel size, which has to be the same along the three axes (to 1e-3 relative): surface
+distances are computed in isotropic voxel units, so images with anisotropic voxels are refused before anything is segmented."""
 import os
 import sys
 from argparse import ArgumentParser
@@ -53,6 +58,8 @@ def build_parser():
     p.add_argument('--fill_label', type=int, default=None,
                    help='the label value removed voxels take (default: the first label of --labels)')
     p.add_argument('--volumes', default=None, help='write the per-label volumes in mm^3 here (.npy or .csv)')
+    p.add_argument('--native_space', action='store_true',
+                   help="write on each image's own voxel grid (its shape and affine) instead of the 1 mm RAS frame")
     p.add_argument('--truth', default=None, help='ground-truth label map (or folder, sorted like the images): score with Dice')
     p.add_argument('--scores', default=None, help='write the per-label Dice table here (.npy or .csv); needs --truth')
     p.add_argument('--surface_scores', default=None,
@@ -94,6 +101,30 @@ def write_volumes(path, labels, table):
     write_scores(path, labels, table, flag='--volumes')
 
 
+ISOTROPY_TOLERANCE = 1e-3   # relative spread of the three voxel sizes
+
+
+def voxel_sizes(aff):
+    """the three voxel sizes (mm) of an affine: the lengths of the columns of its 3 x 3 part"""
+    return np.sqrt(np.sum(np.asarray(aff, dtype=np.float64)[:3, :3] ** 2, axis=0))
+
+
+def isotropic_voxel_size(aff, what='the image'):
+    """the voxel size of an affine whose three voxel sizes agree to ISOTROPY_TOLERANCE (relative spread); anything else is
+    refused: surface distances are measured in isotropic voxel units"""
+    vox = voxel_sizes(aff)
+    if not np.all(np.isfinite(vox)) or vox.min() <= 0 or (vox.max() - vox.min()) > ISOTROPY_TOLERANCE * vox.mean():
+        raise ValueError('--surface_scores with --native_space needs isotropic voxels: %s has voxels of %s mm; surface distances '
+                         'are measured in isotropic voxel units (score without --native_space, at 1 mm, instead)'
+                         % (what, ' x '.join('%g' % v for v in vox)))
+    return float(vox.mean())
+
+
+def voxel_volume(aff):
+    """mm^3 per voxel: |det| of the affine's 3 x 3 part"""
+    return float(abs(np.linalg.det(np.asarray(aff, dtype=np.float64)[:3, :3])))
+
+
 def main(argv=None):
     parser = build_parser()
     args = parser.parse_args(argv)
@@ -118,15 +149,23 @@ def main(argv=None):
     from synthsr_amd.predict_segmentation import predict_segmentation, dice_scores, label_values, mean_dice
     labels = label_values(args.labels)
     lr_pairs = None if args.lr_pairs is None else np.load(args.lr_pairs)
+    affines = None
+    if args.native_space and (args.volumes is not None or args.surface_scores is not None):
+        images = V.list_images_in_folder(os.path.abspath(args.path_images))     # the order predict_segmentation works in
+        affines = [V.load_volume(p, im_only=False)[1] for p in images]
+    sizes = None
+    if args.native_space and args.surface_scores is not None:
+        sizes = [isotropic_voxel_size(a, p) for a, p in zip(affines, images)]
     outs = predict_segmentation(args.path_images, args.path_segmentations, args.model, labels,
                                 path_posteriors=args.posteriors, lr_pairs=lr_pairs, disable_flipping=args.disable_flipping,
                                 n_levels=args.n_levels, nb_conv_per_level=args.nb_conv_per_level,
                                 unet_feat_count=args.unet_feat_count, feat_multiplier=args.feat_multiplier,
                                 activation=args.activation, dtype=args.dtype, keep_largest=keep_largest,
-                                connectivity=args.connectivity, fill_label=args.fill_label)
+                                connectivity=args.connectivity, fill_label=args.fill_label, native_space=args.native_space)
     if args.volumes is not None:
         from synthsr_amd.predict_segmentation import label_volumes
-        write_volumes(args.volumes, labels, np.stack([label_volumes(o, labels) for o in outs]))   # written at 1 mm
+        per_voxel = [1.0] * len(outs) if affines is None else [voxel_volume(a) for a in affines]   # 1.0: written at 1 mm
+        write_volumes(args.volumes, labels, np.stack([label_volumes(o, labels, v) for o, v in zip(outs, per_voxel)]))
     if args.truth is None:
         return None
     truths = V.list_images_in_folder(os.path.abspath(args.truth))
@@ -136,7 +175,8 @@ def main(argv=None):
     surface = None
     if args.surface_scores is not None:
         from synthsr_amd.predict_segmentation import surface_distances, mean_surface_scores, SURFACE_KEYS
-        per_volume = [surface_distances(o, t, labels, percentile=args.surface_percentile) for o, t in zip(outs, truths)]
+        per_volume = [surface_distances(o, t, labels, percentile=args.surface_percentile, voxel_size=v)
+                      for o, t, v in zip(outs, truths, sizes or [1.0] * len(outs))]
         surface = np.stack([np.stack([s[key] for key in SURFACE_KEYS]) for s in per_volume])
     for i, (o, row) in enumerate(zip(outs, table)):
         print(o)

@@ -18,6 +18,7 @@ SOURCES = [('generator.hip', ['-ffp-contract=off']),
            ('ssim.hip', []),
            ('seg_surface.hip', []),
            ('seg_components.hip', []),
+           ('seg_resample.hip', []),
            ('critic.hip', []),
            ('conv_bf16.hip', []),
            ('conv_split.hip', []),

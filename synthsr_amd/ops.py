@@ -1113,6 +1113,52 @@ def seg_keep_largest(labels, comp, lut, G, fill_value, out=None, stats=None, wor
     return out, stats
 
 
+def seg_resample_argmax(probs, box, M, out_shape, labels, fill_value, want_probs=False, out=None, probs_out=None):
+    """The label map on another voxel grid, from posteriors: `out`, int32 of `out_shape`, and with want_probs also the
+    interpolated posteriors, float32 [*out_shape, N].  probs: float32 [s0, s1, s2, N] (channel last); box: (lo0, lo1, lo2, hi0,
+    hi1, hi2), inclusive, the part of the source that holds the volume; M: 3 x 4 (or 4 x 4) float64 on the host, output voxel
+    index -> source voxel coordinates; labels: int32 [N], channel -> label value.  A voxel that M maps more than half a voxel
+    outside the box gets fill_value and zero posteriors; the others the label of the largest trilinearly interpolated posterior,
+    the lowest channel on equal values (include/synthsr_hip.h: synthsr_seg_resample_argmax)."""
+    if probs.dtype != torch.float32 or labels.dtype != torch.int32:
+        raise ValueError('seg_resample_argmax takes the posteriors as float32 and the label values as int32 (got %s, %s)'
+                         % (probs.dtype, labels.dtype))
+    if probs.dim() != 4 or not all(1 <= int(s) <= SURFACE_MAX_SIDE for s in probs.shape[:3]):
+        raise ValueError('seg_resample_argmax: posteriors [s0, s1, s2, N] with sides 1 .. %d, got shape %s'
+                         % (SURFACE_MAX_SIDE, tuple(probs.shape)))
+    N = int(probs.shape[3])
+    if not 2 <= N <= 64 or labels.numel() != N:
+        raise ValueError('seg_resample_argmax: 2 <= N <= 64 channels and one label value per channel (got N = %d, %d label values)'
+                         % (N, labels.numel()))
+    out_shape = tuple(int(s) for s in out_shape)
+    if len(out_shape) != 3 or not all(1 <= s <= SURFACE_MAX_SIDE for s in out_shape):
+        raise ValueError('seg_resample_argmax: out_shape [d0, d1, d2] with sides 1 .. %d, got %s' % (SURFACE_MAX_SIDE, out_shape))
+    box = [int(b) for b in np.asarray(box).reshape(-1)]
+    if len(box) != 6 or not all(0 <= box[a] <= box[3 + a] < int(probs.shape[a]) for a in range(3)):
+        raise ValueError('seg_resample_argmax: box (lo0, lo1, lo2, hi0, hi1, hi2) with 0 <= lo <= hi inside the source %s, got %s'
+                         % (tuple(probs.shape[:3]), box))
+    M = np.asarray(M, dtype=np.float64)
+    if M.shape not in ((3, 4), (4, 4)) or not np.all(np.isfinite(M)):
+        raise ValueError('seg_resample_argmax: M should be a finite 3 x 4 (or 4 x 4) matrix')
+    M = np.ascontiguousarray(M[:3])
+    if not -2 ** 31 <= int(fill_value) < 2 ** 31:
+        raise ValueError('seg_resample_argmax: fill_value should fit int32 (got %r)' % (fill_value,))
+    nvox = out_shape[0] * out_shape[1] * out_shape[2]
+    if out is None:
+        out = torch.empty(out_shape, dtype=torch.int32, device=probs.device)
+    if out.numel() != nvox or out.dtype != torch.int32:
+        raise ValueError('seg_resample_argmax: out should be int32 with one value per output voxel')
+    if want_probs and probs_out is None:
+        probs_out = torch.empty(out_shape + (N,), dtype=torch.float32, device=probs.device)
+    if probs_out is not None and (probs_out.numel() != nvox * N or probs_out.dtype != torch.float32):
+        raise ValueError('seg_resample_argmax: probs_out should be float32 [%d, %d, %d, %d]' % (out_shape + (N,)))
+    _lib.check(_L().synthsr_seg_resample_argmax(_lib.ptr(probs), _lib.i3(probs.shape[:3]), N, (ctypes.c_int * 6)(*box),
+                                                M.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), _lib.i3(out_shape),
+                                                _lib.ptr(labels), int(fill_value), _lib.ptr(out), _lib.ptr(probs_out),
+                                                _lib.stream()), 'seg_resample_argmax')
+    return (out, probs_out) if (want_probs or probs_out is not None) else out
+
+
 def adam_step(p, g, m, v, lr_t, beta1=0.9, beta2=0.999, eps=1e-7, grad_scale=1.0):
     lib = _L()
     _lib.check(lib.synthsr_adam_step(_lib.ptr(p), _lib.ptr(g), _lib.ptr(m), _lib.ptr(v), p.numel(), float(lr_t),

@@ -12,6 +12,10 @@ inside the head kernel and writes the label map of the average.  Without it no p
 Asked to (keep_largest), the label map is cleaned on the device before it is written: of every group of labels only the
 largest connected component stays (ops.seg_components, ops.seg_keep_largest), the rest takes the fill label.
 
+Asked to (native_space), the label map is written on the input image's own voxel grid instead of the 1 mm RAS frame: the
+1 mm posteriors are interpolated onto that grid and the argmax is taken there, in one kernel that keeps the interpolated
+posteriors in registers (ops.seg_resample_argmax; native_grid_affine composes the matrix).  The filter then runs on that map.
+
 The head's channel order is `segmentation_label_list`, as in training_segmentation().  fp32 only."""
 import os
 import numpy as np
@@ -133,6 +137,20 @@ def _filter_on_device(seg, lut, G, fill_value, connectivity):
     return ops.seg_keep_largest(seg, comp, lut_d, G, fill_value, workspace=workspace)
 
 
+def native_grid_affine(aff_native, aff_ras, idx):
+    """float64 [3, 4]: voxel index of the image as it was loaded (affine `aff_native`) -> voxel coordinates of the padded 1 mm
+    RAS array predict.prepare_volume built from it (`aff_ras`: the affine it returned, `idx`: its padding offsets).  Both affines
+    map the centre of voxel (0, 0, 0) to the translation column, the convention volumes.resample_volume and align_volume_to_ref
+    keep, so the matrix is inv(aff_ras) @ aff_native with idx added to its translation."""
+    aff_native, aff_ras = np.asarray(aff_native, dtype=np.float64), np.asarray(aff_ras, dtype=np.float64)
+    idx = np.asarray(idx, dtype=np.float64).reshape(-1)
+    if aff_native.shape != (4, 4) or aff_ras.shape != (4, 4) or idx.shape != (3,):
+        raise ValueError('native_grid_affine takes two 4 x 4 affines and three padding offsets')
+    M = (np.linalg.inv(aff_ras) @ aff_native)[:3].copy()
+    M[:, 3] += idx
+    return M
+
+
 def check_head_width(state, table, labels):
     """the weight file's head should have one channel per listed label"""
     name = table.head['w']
@@ -191,7 +209,7 @@ class SegmentationPredictor:
         return self.nets[key]
 
     def segment_volume(self, S, flipping=True, lr_pairs=None, return_posteriors=False, keep_largest=None, connectivity=6,
-                       fill_label=None, crop=None):
+                       fill_label=None, crop=None, native=None):
         """S [W0,W1,W2] (numpy, padded: every side a multiple of 2**(n_levels-1)) -> int32 label map [W0,W1,W2] of label
         values (numpy); with return_posteriors also the posteriors [W0,W1,W2,N] float32 the map is the argmax of.
         flipping: average with the pass on the volume flipped along the first (left-right) axis, the channels of each
@@ -200,7 +218,13 @@ class SegmentationPredictor:
         keep_largest: None, or a grouping of component_groups() ('per_label', 'foreground', group ids per channel): the
         returned (cropped) map keeps only the largest connected component of every group under `connectivity` (6, 18, 26), the
         other voxels of the group become `fill_label` (default: the first listed label).  The filter runs on the device.  The
-        posteriors are returned unchanged: they are those of the unfiltered map."""
+        posteriors are returned unchanged: they are those of the unfiltered map.
+        native: None, or (M, out_shape): the map is returned on another voxel grid of shape out_shape, M (3 x 4, float64) taking
+        a voxel index of that grid to voxel coordinates of S (native_grid_affine).  The posteriors of S are always formed then;
+        they are interpolated at every voxel of the grid and the map is their argmax there (ops.seg_resample_argmax), `crop`
+        being the box that is interpolated in: voxels that fall more than half a voxel outside it get `fill_label` (default: the
+        first listed label) and zero posteriors.  The returned posteriors are the interpolated ones [*out_shape, N], and the
+        filter runs on the grid's map."""
         import torch
         perm = lr_permutation(self.labels, lr_pairs)
         grouping = None if keep_largest is None else component_groups(self.labels, keep_largest, fill_label)
@@ -215,6 +239,27 @@ class SegmentationPredictor:
             self._labels_dev = torch.from_numpy(self.labels).to(net.device)
         x = torch.from_numpy(np.ascontiguousarray(S, dtype=np.float32)).to(net.device)[..., None].contiguous()
         probs = None
+        if native is not None:
+            from . import ops
+            M, out_shape = native
+            fill_value = component_groups(self.labels, 'foreground', fill_label)[2]
+            box = [0, 0, 0] + [int(n) - 1 for n in S.shape]
+            if crop is not None:
+                spans = [sl.indices(int(n)) for sl, n in zip(crop, S.shape)]
+                if any(step != 1 or stop <= start for start, stop, step in spans):
+                    raise ValueError('crop should be three non-empty slices of step 1, got %r' % (crop,))
+                box = [sp[0] for sp in spans] + [sp[1] - 1 for sp in spans]
+            probs = net.predict_probs(x)
+            if flipping:
+                probs = net.predict_labels(torch.flip(x, dims=[0]).contiguous(), self._labels_dev, prev=probs,
+                                           perm=torch.from_numpy(perm).to(net.device), want_probs=True)[1]
+            res = ops.seg_resample_argmax(probs.view(*S.shape, N), box, M, out_shape, self._labels_dev, fill_value,
+                                          want_probs=return_posteriors)
+            out, probs = res if return_posteriors else (res, None)
+            if grouping is not None:
+                out = _filter_on_device(out, grouping[0], grouping[1], grouping[2], connectivity)[0]
+            seg = out.cpu().numpy().astype(np.int32, copy=False)
+            return (seg, probs.cpu().numpy()) if return_posteriors else seg
         if flipping:
             prev = net.predict_probs(x)
             out = net.predict_labels(torch.flip(x, dims=[0]).contiguous(), self._labels_dev, prev=prev,
@@ -248,7 +293,7 @@ def _suffixed(path, suffix):
 def predict_segmentation(path_images, path_segmentations, path_model, segmentation_label_list, path_posteriors=None,
                          lr_pairs=None, disable_flipping=False, n_levels=5, nb_conv_per_level=2, unet_feat_count=24,
                          feat_multiplier=2, activation='elu', device=None, verbose=True, predictor=None, dtype='f32',
-                         keep_largest=None, connectivity=6, fill_label=None):
+                         keep_largest=None, connectivity=6, fill_label=None, native_space=False):
     """The file / folder contract of predict.predict(): `path_images` / `path_segmentations` (and `path_posteriors`, if
     given) are all single files (.nii, .nii.gz, .mgz, .npz) or all folders; in folders the outputs carry the suffixes
     `_seg` and `_posteriors`.  Label maps are saved as int32 in the 1 mm RAS frame predict() writes in.  Returns the paths
@@ -257,7 +302,11 @@ def predict_segmentation(path_images, path_segmentations, path_model, segmentati
     keep_largest: None (the raw argmax), or a grouping of component_groups(): the label map that is written keeps only the largest
     connected component of every group under `connectivity`, the other voxels of the group become `fill_label` (default: the first
     listed label).  The filter runs on the device on the cropped map, so the file equals keep_largest_components() of the file
-    written without it.  Posteriors, when asked for, are written unchanged."""
+    written without it.  Posteriors, when asked for, are written unchanged.
+    native_space: label maps and posteriors are written with the input image's own shape and affine instead: the 1 mm posteriors
+    are interpolated onto the input's voxel grid and the argmax is taken there (SegmentationPredictor.segment_volume: native);
+    voxels of the input that lie outside the resampled volume get `fill_label`.  The filter then runs on that map.  For 3-D
+    images."""
     if dtype not in ('f32', 'bf16'):
         raise ValueError("dtype should be 'f32' or 'bf16', got %r" % (dtype,))
     if 32 % (2 ** (int(n_levels) - 1)) != 0:
@@ -293,13 +342,18 @@ def predict_segmentation(path_images, path_segmentations, path_model, segmentati
         im, aff, _ = V.load_volume(pin, im_only=False, dtype='float')
         S, idx, shape, aff2 = prepare_volume(im, aff)
         crop = tuple(slice(int(o), int(o) + int(n)) for o, n in zip(idx, shape))
+        native, aff_out = None, aff2
+        if native_space:
+            if np.ndim(im) != 3:
+                raise ValueError('native_space takes 3-D images, %s has shape %s' % (pin, np.shape(im)))
+            native, aff_out = (native_grid_affine(aff, aff2, idx), np.shape(im)), aff
         res = predictor.segment_volume(S, flipping=not disable_flipping, lr_pairs=lr_pairs,
                                        return_posteriors=ppost is not None, keep_largest=keep_largest,
-                                       connectivity=connectivity, fill_label=fill_label, crop=crop)
+                                       connectivity=connectivity, fill_label=fill_label, crop=crop, native=native)
         seg = res[0] if ppost is not None else res
-        V.save_volume(np.ascontiguousarray(seg), aff2, None, pout, dtype='int32')
+        V.save_volume(np.ascontiguousarray(seg), aff_out, None, pout, dtype='int32')
         if ppost is not None:
-            V.save_volume(np.ascontiguousarray(res[1]), aff2, None, ppost, dtype='float32', n_dims=3)
+            V.save_volume(np.ascontiguousarray(res[1]), aff_out, None, ppost, dtype='float32', n_dims=3)
     return outs
 
 
