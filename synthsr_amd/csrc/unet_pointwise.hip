@@ -114,6 +114,16 @@ __device__ __forceinline__ void block_scalar_add(float v, float* slot) {
   __syncthreads();
 }
 
+// BatchNorm backward of one gradient value: gamma * invstd * (g - sum_dy / n - xhat * sum_dyxhat / n).  The roundings are spelled
+// out (two fused multiply-adds, every other product rounded on its own) and contraction is off inside, so that every kernel that
+// calls this gets the same bits from the same operands: left to the compiler, bn_pool_elu_bwd_kernel fused s0 * inv_n into the
+// subtraction for the first voxel of a window and hoisted it as a rounded product for the other seven.
+__device__ __forceinline__ float bn_bwd_map(float g, float xh, float gam, float inv, float s0, float s1, float inv_n) {
+#pragma clang fp contract(off)
+  const float t = fmaf(-(xh * s1), inv_n, fmaf(-s0, inv_n, g));
+  return gam * inv * t;
+}
+
 // ------------------------------------------------------------------------------------------ ELU backward
 // dz = (dy [+ dy2]) * elu'(y); dbias[c] += sum dz
 // Optional fused BatchNorm backward (bn_sums != nullptr): the incoming gradient is w.r.t. the BN OUTPUT of y and is
@@ -158,7 +168,7 @@ __global__ __launch_bounds__(RB) void elu_bwd_kernel(const T* __restrict__ dy, c
       for (int k = 0; k < 4; ++k) {
         const float inv = rsqrtf(bn_stats[C + c + k] + eps);
         const float xh = (aa[k] - bn_stats[c + k]) * inv;
-        gg[k] = bn_gamma[c + k] * inv * (gg[k] - bn_sums[c + k] * inv_n - xh * bn_sums[C + c + k] * inv_n);
+        gg[k] = bn_bwd_map(gg[k], xh, bn_gamma[c + k], inv, bn_sums[c + k], bn_sums[C + c + k], inv_n);
       }
       g = make_float4(gg[0], gg[1], gg[2], gg[3]);
     }
@@ -208,17 +218,35 @@ __global__ __launch_bounds__(256) void scale_channels_kernel(const T* __restrict
 }
 
 // ------------------------------------------------------------------------------------------ BN statistics
+// Shifted data: the sums are those of x - k and (x - k)^2 with k[c] the mean of the channel's first (up to) 32 values, so that
+// E[(x - k)^2] - E[x - k]^2 does not cancel when the mean dwarfs the spread (at mean 50, deviation 1 the fp32 squares ~2500
+// each carried 1.5e-4 and the variance came back 7e-4 off); k lies inside the data, so |mean - k| is at most its range.
+// Every workgroup and bn_stats_finalize_kernel, which adds k back to the mean, get k from bn_stats_shift: the same bits.
+__device__ __forceinline__ float ld1(const float* p) { return *p; }
+__device__ __forceinline__ float ld1(const bf16_t* p) { return bf2f(p->v); }
+template <typename T>
+__device__ __forceinline__ float bn_stats_shift(const T* __restrict__ x, int64_t nvox, int C, int c) {
+  const int m = nvox < 32 ? (int)nvox : 32;
+  float s = 0.f;
+  for (int v = 0; v < m; ++v) s += ld1(x + (int64_t)v * C + c);
+  return s / (float)m;
+}
 template <typename T>
 __global__ __launch_bounds__(RB) void bn_stats_kernel(const T* __restrict__ x, int64_t n4, int C4,
                                                       double* __restrict__ ws) {
-  extern __shared__ float smem[];  // [2][C4*4]
+  extern __shared__ float smem[];  // [2][C4*4] sums, [C4*4] shift
   const bool fixed = (RB % C4) == 0;
+  float* ks = smem + 2 * C4 * 4;
   for (int i = threadIdx.x; i < 2 * C4 * 4; i += RB) smem[i] = 0.f;
+  for (int c = threadIdx.x; c < C4 * 4; c += RB) ks[c] = bn_stats_shift(x, n4 / C4, C4 * 4, c);
   __syncthreads();
   float4 part[2] = {make_float4(0.f, 0.f, 0.f, 0.f), make_float4(0.f, 0.f, 0.f, 0.f)};
   const int64_t stride = (int64_t)gridDim.x * RB;
+  const float4 kf = ld4(ks + (threadIdx.x % C4) * 4);  // fixed: a thread stays with one channel group
   for (int64_t i = blockIdx.x * (int64_t)RB + threadIdx.x; i < n4; i += stride) {
-    const float4 a = ld4(x + i * 4);
+    const float4 k = fixed ? kf : ld4(ks + (i % C4) * 4);
+    float4 a = ld4(x + i * 4);
+    a.x -= k.x; a.y -= k.y; a.z -= k.z; a.w -= k.w;
     if (fixed) {
       part[0].x += a.x; part[0].y += a.y; part[0].z += a.z; part[0].w += a.w;
       part[1].x += a.x * a.x; part[1].y += a.y * a.y; part[1].z += a.z * a.z; part[1].w += a.w * a.w;
@@ -240,13 +268,17 @@ __global__ __launch_bounds__(RB) void bn_stats_kernel(const T* __restrict__ x, i
   syn_det_gather_end(2 * C4 * 4);
 }
 
-__global__ void bn_stats_finalize_kernel(const double* __restrict__ ws, float* __restrict__ stats, int C, double inv_n) {
+template <typename T>
+__global__ void bn_stats_finalize_kernel(const double* __restrict__ ws, const T* __restrict__ x, float* __restrict__ stats, int C,
+                                         int64_t nvox) {
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c < C) {
-    const double m = ws[c] * inv_n;
+    const double inv_n = 1.0 / (double)nvox;
+    const float k = bn_stats_shift(x, nvox, C, c);
+    const double m = ws[c] * inv_n;  // mean and mean square of x - k
     double v = ws[C + c] * inv_n - m * m;
     if (v < 0.0) v = 0.0;
-    stats[c] = (float)m;
+    stats[c] = (float)((double)k + m);
     stats[C + c] = (float)v;
   }
 }
@@ -491,7 +523,7 @@ __global__ __launch_bounds__(RB) void bn_pool_elu_bwd_kernel(const T* __restrict
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
         const float xh = (aa[q] - mean[q]) * inv[q];
-        gg[q] = gam[q] * inv[q] * (gg[q] - s0[q] * inv_n - xh * s1[q] * inv_n);  // the expression of elu_bwd_kernel, bit for bit
+        gg[q] = bn_bwd_map(gg[q], xh, gam[q], inv[q], s0[q], s1[q], inv_n);  // as elu_bwd_kernel, bit for bit
       }
       if (dy2) {
         const float4 g2 = ld4(dy2 + vi * C + c);
@@ -2136,11 +2168,11 @@ int bn_stats_t(const T* x, int64_t nvox, int C, float* stats, double* ws, synths
   if (!x || !stats || !ws || nvox < 1 || !ok_c4(C)) return SYNTHSR_EINVAL;
   if (hipMemsetAsync(ws, 0, 2 * C * sizeof(double), (hipStream_t)stream) != hipSuccess) return SYNTHSR_ELAUNCH;
   const int64_t n4 = nvox * (C / 4);
-  hipLaunchKernelGGL(bn_stats_kernel<T>, dim3(syn_grid(n4, RB, red_grid())), dim3(RB), 2 * C * sizeof(float),
+  hipLaunchKernelGGL(bn_stats_kernel<T>, dim3(syn_grid(n4, RB, red_grid())), dim3(RB), 3 * C * sizeof(float),
                      (hipStream_t)stream, x, n4, C / 4, ws);
   SYN_CHECK_LAUNCH();
-  hipLaunchKernelGGL(bn_stats_finalize_kernel, dim3((C + 63) / 64), dim3(64), 0, (hipStream_t)stream, ws, stats, C,
-                     1.0 / (double)nvox);
+  hipLaunchKernelGGL(bn_stats_finalize_kernel<T>, dim3((C + 63) / 64), dim3(64), 0, (hipStream_t)stream, ws, x, stats, C,
+                     nvox);
   SYN_CHECK_LAUNCH();
   return SYNTHSR_OK;
 }
