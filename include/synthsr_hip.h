@@ -651,6 +651,35 @@ int synthsr_seg_head_dice_bwd_weighted(const float* probs, const int32_t* seg, c
                                        const float* class_weights, float scale, float* dbn, float* dw, float* db,
                                        synthsr_stream_t stream);
 
+/* --- the two other losses of a softmax-headed segmentation U-Net, taken on the LOGITS (fp32) -----------------------------
+ * WeightedL2Loss (ext/lab2im/layers.py:1408-1412; the warm-up such networks are started with) and CrossEntropyLoss (:1498-1526,
+ * enable_checks=False, no class or boundary weights).  x, stats / gamma / beta / eps, w, b, seg, lut as for the soft Dice; a voxel
+ * outside the table or mapped to -1 has an all-zero ground-truth row.  C <= 64 with C % 4 == 0, 2 <= N <= 64, kind one of the
+ * two constants: anything else (NULL pointers included) returns SYNTHSR_EINVAL before any launch.  Nothing is allocated and no
+ * per-voxel intermediate exists: fwd reads x and seg (4 nvox (C + 1) bytes) and adds to sums [3] (zeroed by the caller); bwd
+ * reads x once, forms the logits again and writes dbn (4 nvox (2 C + 1) bytes).
+ * With z[v][n] = bn(x[v]) . w[:, n] + b[n], k(v) the class of voxel v or -1, gt_n = [k(v) == n]:
+ * SYNTHSR_SEG_LOSS_WL2 (t = target_value): a_v = 1e-8f where k(v) == 0, else 1.0f (1 - gt_0 + 1e-8 in fp32; a voxel without
+ *      a class has weight 1 and target -t in every channel);
+ *      fwd: sums[0] += a_v sum_n (z_n - t (2 gt_n - 1))^2, sums[1] += [k != 0], sums[2] += [k == 0];
+ *      loss = sums[0] / (W N), W = sums[1] + 1e-8 sums[2];   bwd: dz_n = scale 2 a_v (z_n - t (2 gt_n - 1)) / (W N).
+ * SYNTHSR_SEG_LOSS_CE (target_value ignored): fwd: sums[0] += -log p_k(v) over the voxels with a class, sums[1] += their number,
+ *      sums[2] unused; loss = sums[0] / nvox (the mean over ALL voxels);   bwd: dz_n = scale (p_n - gt_n) / nvox on voxels with a
+ *      class, 0 elsewhere.  log p is taken as a log-softmax (z_k - max - log sum exp): where a posterior underflows to 0 in fp32
+ *      the reference's unclipped log gives inf and this stays finite -- the only departure from it.
+ * bwd, both kinds: dbn[v][c] = sum_n dz_n w[c][n] written; dw [C][N], db [N] accumulated (dw[c][n] += gamma[c] A[n][c] +
+ *      beta[c] Bs[n], db[n] += Bs[n], A[n][c] = sum_v dz_n xhat[v][c], Bs[n] = sum_v dz_n); sums as fwd left them. */
+#define SYNTHSR_SEG_LOSS_WL2 0
+#define SYNTHSR_SEG_LOSS_CE 1
+int synthsr_seg_head_logit_loss_fwd(const float* x, int64_t nvox, int C, const float* stats, const float* gamma,
+                                    const float* beta, float eps, const float* w, const float* b, int N, const int32_t* seg,
+                                    const int32_t* lut, int lut_n, int kind, float target_value, float* sums,
+                                    synthsr_stream_t stream);
+int synthsr_seg_head_logit_loss_bwd(const int32_t* seg, const int32_t* lut, int lut_n, const float* x, int64_t nvox, int C, int N,
+                                    const float* stats, const float* gamma, const float* beta, float eps, const float* w,
+                                    const float* b, int kind, float target_value, const float* sums, float scale, float* dbn,
+                                    float* dw, float* db, synthsr_stream_t stream);
+
 /* --- segmenting with a trained softmax-headed U-Net, scoring label maps (fp32) ------------------------------------------
  * x, stats / gamma / beta / eps (inference: the moving statistics), w, b as above; labels [N]: head channel -> label VALUE.
  * C <= 64 with C % 4 == 0, 2 <= N <= 64 (label_counts: 1 <= N <= 64): anything else returns SYNTHSR_EINVAL before any launch.

@@ -35,6 +35,11 @@ def build_parser():
     parser.add_argument('--dice_boundary_weights', dest='dice_boundary_weights', type=float, default=0.)
     parser.add_argument('--dice_boundary_dist', dest='dice_boundary_dist', type=int, default=3)
     parser.add_argument('--dice_no_skip_background', dest='dice_skip_background', action='store_false')
+    # the other losses: WeightedL2Loss on the logits for the first epochs (the warm-up), then the Dice or the cross-entropy
+    parser.add_argument('--wl2_epochs', dest='wl2_epochs', type=int, default=0)
+    parser.add_argument('--wl2_target_value', dest='wl2_target_value', type=float, default=5.)
+    parser.add_argument('--segmentation_loss', dest='segmentation_loss', type=str, default='dice',
+                        choices=('dice', 'cross_entropy'))
     return parser
 
 

@@ -147,6 +147,10 @@ SIGNATURES = {
                                                    c_float, _P, _P, _S]),
     'synthsr_seg_head_dice_bwd_weighted': (c_int, [_P, _P, _P, c_int, _P, c_int64, c_int, c_int, _P, _P, _P, c_float, _P, _P, _P,
                                                    c_float, _P, c_float, _P, _P, _P, _S]),
+    'synthsr_seg_head_logit_loss_fwd': (c_int, [_P, c_int64, c_int, _P, _P, _P, c_float, _P, _P, c_int, _P, _P, c_int, c_int,
+                                                c_float, _P, _S]),
+    'synthsr_seg_head_logit_loss_bwd': (c_int, [_P, _P, c_int, _P, c_int64, c_int, c_int, _P, _P, _P, c_float, _P, _P, c_int,
+                                                c_float, _P, c_float, _P, _P, _P, _S]),
     'synthsr_seg_head_argmax': (c_int, [_P, c_int64, c_int, _P, _P, _P, c_float, _P, _P, c_int, _P, _P, _S]),
     'synthsr_seg_head_tta_argmax': (c_int, [_P, POINTER(c_int), c_int, _P, _P, _P, c_float, _P, _P, c_int, _P, _P, _P, _P, _P,
                                             _S]),

@@ -1581,10 +1581,11 @@ __device__ __forceinline__ void shd_row_logits(float (&val)[4], const shd_f32x4 
   }
 }
 
-// softmax of that row: val[nb] <- exp(val[nb] - max) (0 past N); returns 1 / their sum, p = val[nb] * that
-__device__ __forceinline__ float shd_row_softmax(float (&val)[4], int NB, int N) {
+// softmax of that row: val[nb] <- exp(val[nb] - max) (0 past N); returns 1 / their sum, p = val[nb] * that.  mx <- the row's
+// maximum: log p_n = z_n - mx + log(1 / sum), finite where p_n itself underflows
+__device__ __forceinline__ float shd_row_softmax(float (&val)[4], int NB, int N, float& mx) {
   const int col = threadIdx.x & 15;
-  float mx = -INFINITY;
+  mx = -INFINITY;
 #pragma unroll
   for (int nb = 0; nb < 4; ++nb) mx = fmaxf(mx, val[nb]);
 #pragma unroll
@@ -1598,6 +1599,10 @@ __device__ __forceinline__ float shd_row_softmax(float (&val)[4], int NB, int N)
 #pragma unroll
   for (int o = 1; o < 16; o <<= 1) den += __shfl_xor(den, o, 64);
   return 1.f / den;
+}
+__device__ __forceinline__ float shd_row_softmax(float (&val)[4], int NB, int N) {
+  float mx;
+  return shd_row_softmax(val, NB, N, mx);
 }
 
 // probs[v][n] = softmax_n(bn(x[v]) . w + b), sums[n] += 2 gt p, sums[N + n] += gt^2 + p^2: one pass, every voxel read once.
@@ -1832,6 +1837,261 @@ __global__ __launch_bounds__(256) void seg_head_dice_bwd_kernel(const float* __r
         float g = (k == n ? sga[n] : 0.f) - p * sgb[n];
         if constexpr (WEIGHTED) g *= ((m >> n) & 1ull) ? wb : 1.f;
         dlw[r * SN + n] = p * (g - S);
+      }
+    }
+    __syncthreads();
+    if (lane < N) {
+      float t = 0.f;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) t += dlw[r * SN + lane];
+      bs += t;
+    }
+    shd_f32x4 accD[4];
+#pragma unroll
+    for (int cb = 0; cb < 4; ++cb) accD[cb] = shd_f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int n0 = 0; n0 < NB * 16; n0 += 4) {  // dbn [16 voxels][16 channels] per channel block, K = classes
+      const float a = dlw[col * SN + n0 + quad];
+#pragma unroll
+      for (int cb = 0; cb < 4; ++cb)
+        if (cb < CB) accD[cb] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, wl[(n0 + quad) * SW + cb * 16 + col], accD[cb], 0, 0, 0);
+    }
+#pragma unroll
+    for (int cb = 0; cb < 4; ++cb) {
+      const int c = cb * 16 + col;
+      if (cb < CB && c < C) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int64_t v = v0 + 4 * quad + r;
+          if (v < nvox) dbn[v * C + c] = accD[cb][r];
+        }
+      }
+    }
+#pragma unroll
+    for (int k0 = 0; k0 < 16; k0 += 4) {  // A [16 classes][16 channels] per block pair, K = the 16 voxels
+      float a[4], bx[4];
+#pragma unroll
+      for (int nb = 0; nb < 4; ++nb) a[nb] = nb < NB ? dlw[(k0 + quad) * SN + nb * 16 + col] : 0.f;
+#pragma unroll
+      for (int cb = 0; cb < 4; ++cb) bx[cb] = cb < CB ? xw[(k0 + quad) * SX + cb * 16 + col] : 0.f;
+#pragma unroll
+      for (int nb = 0; nb < 4; ++nb)
+#pragma unroll
+        for (int cb = 0; cb < 4; ++cb)
+          if (nb < NB && cb < CB) accA[nb][cb] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[nb], bx[cb], accA[nb][cb], 0, 0, 0);
+    }
+  }
+  // the four waves add their A | Bs in wave order into part (over dl | xs), then ONE flush per workgroup
+  __syncthreads();
+  float* part = dl;
+  for (int w = 0; w < 4; ++w) {
+    if (wave == w) {
+#pragma unroll
+      for (int nb = 0; nb < 4; ++nb)
+#pragma unroll
+        for (int cb = 0; cb < 4; ++cb)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const int n = nb * 16 + 4 * quad + r, c = cb * 16 + col;
+            if (nb < NB && cb < CB && n < N && c < C) part[n * C + c] = (w ? part[n * C + c] : 0.f) + accA[nb][cb][r];
+          }
+      if (lane < N) part[N * C + lane] = (w ? part[N * C + lane] : 0.f) + bs;
+    }
+    __syncthreads();
+  }
+  if (syn_det_gather(part, N * C + N)) {
+    for (int i = tid; i < C * N; i += 256) {
+      const int c = i / N, n = i - c * N;
+      atomicAdd(&dw[i], gamma[c] * part[n * C + c] + beta[c] * part[N * C + n]);
+    }
+    if (tid < N) atomicAdd(&db[tid], part[N * C + tid]);
+  }
+  syn_det_gather_end(N * C + N);
+}
+
+// ------------------------------------------------------------------ trainable softmax head + losses on the logits (fp32)
+// WeightedL2Loss (ext/lab2im/layers.py:1408-1412) and CrossEntropyLoss (:1498-1526, enable_checks=False, no weights) of the
+// logits z[v][n] = bn(x[v]) . w[:, n] + b[n] against the one-hot of k(v) = shd_class(seg[v]) (-1: an all-zero row).  The gradient
+// of a voxel needs nothing of the other voxels but three sums, so neither kernel has a per-voxel intermediate: the forward one
+// reads x and seg and writes three floats, the backward one reads x once, forms the logits again and writes dbn.  KIND is
+// SYNTHSR_SEG_LOSS_WL2 / _CE (include/synthsr_hip.h).
+//   WL2: a_v = 1e-8 where k(v) == 0, else 1 (1 - gt_0 + 1e-8 in fp32); sums[0] += a_v sum_n (z_n - t (2 gt_n - 1))^2,
+//        sums[1] += [k != 0], sums[2] += [k == 0]; loss = sums[0] / (W N), W = sums[1] + 1e-8 sums[2];
+//        dz_n = scale 2 a_v (z_n - t (2 gt_n - 1)) / (W N)
+//   CE:  sums[0] += -log p_k(v) over the classed voxels as a log-softmax (z_k - max - log sum exp: finite where p_k underflows
+//        and the reference's log gives inf), sums[1] += [k >= 0]; loss = sums[0] / nvox;
+//        dz_n = scale (p_n - gt_n) / nvox on classed voxels, 0 elsewhere
+constexpr int SHD_LOSS_WL2 = SYNTHSR_SEG_LOSS_WL2, SHD_LOSS_CE = SYNTHSR_SEG_LOSS_CE;
+// their LDS: the three sums fit the Dice forward's red | st, the bias the mask words of the weighted Dice backward
+static_assert(ShdFwdLds(4, 2, true).st - ShdFwdLds(4, 2, true).red >= 4 * 4 && ShdFwdLds(4, 2, true).RS >= 3 &&
+              ShdBwdLds(64, 64, true).total - ShdBwdLds(64, 64, true).msk >= 64 &&
+              ShdBwdLds(4, 2, true).total - ShdBwdLds(4, 2, true).msk >= 64,
+              "LDS layout of the logit-loss kernels");
+
+// LDS: ShdFwdLds(C, N, true); of red | st only [4][4] | [4] floats are used.  Nothing is written per voxel.
+template <int KIND>
+__global__ __launch_bounds__(256) void seg_head_logit_loss_fwd_kernel(const float* __restrict__ x, int64_t nvox, int C,
+                                                                      const float* __restrict__ stats,
+                                                                      const float* __restrict__ gamma,
+                                                                      const float* __restrict__ beta, float eps,
+                                                                      const float* __restrict__ W, const float* __restrict__ b,
+                                                                      int N, const int32_t* __restrict__ seg,
+                                                                      const int32_t* __restrict__ lut, int lut_n, float tv,
+                                                                      float* __restrict__ sums) {
+  extern __shared__ float smem[];
+  const ShdFwdLds L(C, N, true);
+  const int NB = (N + 15) >> 4, SX = L.SX, SW = L.SW;
+  float *wl = smem, *ssc = smem + L.scale, *ssh = smem + L.shift, *sb = smem + L.bias, *red = smem + L.red, *st = smem + L.st;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, col = lane & 15, quad = lane >> 4;
+  shd_stage_head(wl, ssc, ssh, sb, SW, C, N, stats, gamma, beta, eps, W, b, [](int n) { return n; });
+  __syncthreads();
+  float* xw = smem + L.xs + wave * 16 * SX;
+  int* cw = reinterpret_cast<int*>(smem + L.cls) + wave * 16;
+  float s[3] = {0.f, 0.f, 0.f};
+  for (int64_t base = (int64_t)blockIdx.x * SHD_TILE; base < nvox; base += (int64_t)gridDim.x * SHD_TILE) {
+    const int64_t v0 = base + wave * 16;
+    shd_stage_rows(xw, SX, x, v0, nvox, C, [&](float a, int c) { return fmaf(a, ssc[c], ssh[c]); });  // BatchNorm output
+    if (lane < 16) cw[lane] = v0 + lane < nvox ? shd_class(seg[v0 + lane], lut, lut_n, N) : -1;
+    __syncthreads();
+    shd_f32x4 acc[4];
+    shd_logits(acc, xw, wl, SX, SW, C, NB);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      float lg[4];
+      shd_row_logits(lg, acc, r, sb, NB, N);
+      const bool in = v0 + 4 * quad + r < nvox;
+      const int k = cw[4 * quad + r];
+      if constexpr (KIND == SHD_LOSS_WL2) {
+        float t = 0.f;
+#pragma unroll
+        for (int nb = 0; nb < 4; ++nb) {
+          const int n = nb * 16 + col;
+          if (nb < NB && n < N) {
+            const float d = lg[nb] - (k == n ? tv : -tv);
+            t = fmaf(d, d, t);
+          }
+        }
+        if (in) {
+          s[0] += (k == 0 ? 1e-8f : 1.f) * t;
+          if (col == 0) {
+            s[1] += k == 0 ? 0.f : 1.f;
+            s[2] += k == 0 ? 1.f : 0.f;
+          }
+        }
+      } else {
+        float zk = 0.f, mx;
+#pragma unroll
+        for (int nb = 0; nb < 4; ++nb)
+          if (nb * 16 + col == k) zk = lg[nb];
+        const float inv = shd_row_softmax(lg, NB, N, mx);
+        if (in && k >= 0) {  // the lane that holds class k: -log p_k = max - z_k + log sum exp
+          if ((k & 15) == col) s[0] += (mx - zk) - logf(inv);
+          if (col == 0) s[1] += 1.f;
+        }
+      }
+    }
+  }
+  // the 64 lanes of a wave, then the four waves in order, then ONE flush per workgroup
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) s[i] += __shfl_xor(s[i], o, 64);
+    if (lane == 0) red[wave * 4 + i] = s[i];
+  }
+  __syncthreads();
+  if (tid < 3) st[tid] = (red[tid] + red[4 + tid]) + (red[8 + tid] + red[12 + tid]);
+  __syncthreads();
+  if (syn_det_gather(st, 3))
+    if (tid < 3) atomicAdd(&sums[tid], st[tid]);
+  syn_det_gather_end(3);
+}
+
+// Backward of scale * loss into the last BatchNorm's output and the head: dz as above, then as seg_head_dice_bwd_kernel does with
+// its dlogit: dbn[v][c] = sum_n dz_n w[c][n] written, A[n][c] = sum_v dz_n xhat[v][c], Bs[n] = sum_v dz_n,
+// dw[c][n] += gamma[c] A[n][c] + beta[c] Bs[n], db[n] += Bs[n].  x is read once, staged as xhat [16][SX] per wave; the A operand of
+// the logits is gamma xhat + beta formed at the read, their B operand the transposed head wl [16 NB][SW] that dbn needs anyway
+// (16 classes x 4 consecutive channels: 64 banks, the A operand's pattern), so that w is in LDS once.
+// LDS: ShdBwdLds(C, N, true): ga | gb hold gamma | beta, the mask words' place the bias [64].
+template <int KIND>
+__global__ __launch_bounds__(256) void seg_head_logit_loss_bwd_kernel(const int32_t* __restrict__ seg,
+                                                                      const int32_t* __restrict__ lut, int lut_n,
+                                                                      const float* __restrict__ x, int64_t nvox, int C, int N,
+                                                                      const float* __restrict__ stats,
+                                                                      const float* __restrict__ gamma,
+                                                                      const float* __restrict__ beta, float eps,
+                                                                      const float* __restrict__ W, const float* __restrict__ b,
+                                                                      float tv, const float* __restrict__ sums, float scale,
+                                                                      float* __restrict__ dbn, float* __restrict__ dw,
+                                                                      float* __restrict__ db) {
+  extern __shared__ float smem[];
+  const ShdBwdLds L(C, N, true);
+  const int NB = L.NB, CB = (C + 15) >> 4, SX = L.SX, SN = L.SN, SW = L.SW;
+  float *wl = smem, *dl = smem + L.dl, *xs = smem + L.xs, *sga = smem + L.ga, *sgb = smem + L.gb, *smean = smem + L.mean,
+        *srstd = smem + L.rstd, *sb = smem + L.msk;
+  int* scls = reinterpret_cast<int*>(smem + L.cls);
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, col = lane & 15, quad = lane >> 4;
+  for (int i = tid; i < NB * 16 * SW; i += 256) {
+    const int n = i / SW, c = i - n * SW;
+    wl[i] = (n < N && c < C) ? W[c * N + n] : 0.f;
+  }
+  for (int i = tid; i < SHD_TILE * (SN + SX); i += 256) dl[i] = 0.f;  // the padding columns stay zero
+  for (int i = tid; i < 64; i += 256) {
+    sga[i] = i < C ? gamma[i] : 0.f;
+    sgb[i] = i < C ? beta[i] : 0.f;
+    sb[i] = i < N ? b[i] : 0.f;
+    if (i < C) {
+      smean[i] = stats[i];
+      srstd[i] = rsqrtf(stats[C + i] + eps);
+    }
+  }
+  const float coef = KIND == SHD_LOSS_WL2 ? 2.f * scale / ((sums[1] + 1e-8f * sums[2]) * (float)N) : scale / (float)nvox;
+  __syncthreads();
+  float* dlw = dl + wave * 16 * SN;
+  float* xw = xs + wave * 16 * SX;
+  int* cw = scls + wave * 16;
+  shd_f32x4 accA[4][4];
+#pragma unroll
+  for (int nb = 0; nb < 4; ++nb)
+#pragma unroll
+    for (int cb = 0; cb < 4; ++cb) accA[nb][cb] = shd_f32x4{0.f, 0.f, 0.f, 0.f};
+  float bs = 0.f;
+  for (int64_t base = (int64_t)blockIdx.x * SHD_TILE; base < nvox; base += (int64_t)gridDim.x * SHD_TILE) {
+    const int64_t v0 = base + wave * 16;
+    shd_stage_rows(xw, SX, x, v0, nvox, C, [&](float a, int c) { return (a - smean[c]) * srstd[c]; });  // xhat
+    if (lane < 16) cw[lane] = v0 + lane < nvox ? shd_class(seg[v0 + lane], lut, lut_n, N) : -1;
+    __syncthreads();
+    {  // logits [16 voxels][16 classes] per class block, K = channels; then dz in the wave's dl rows
+      shd_f32x4 acc[4];
+#pragma unroll
+      for (int nb = 0; nb < 4; ++nb) acc[nb] = shd_f32x4{0.f, 0.f, 0.f, 0.f};
+      for (int c0 = 0; c0 < C; c0 += 4) {
+        const int c = c0 + quad;
+        const float a = fmaf(xw[col * SX + c], sga[c], sgb[c]);
+#pragma unroll
+        for (int nb = 0; nb < 4; ++nb)
+          if (nb < NB) acc[nb] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, wl[(nb * 16 + col) * SW + c], acc[nb], 0, 0, 0);
+      }
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        float lg[4];
+        shd_row_logits(lg, acc, r, sb, NB, N);
+        const int row = 4 * quad + r, k = cw[row];
+        const bool in = v0 + row < nvox;  // rows past the volume: dz = 0
+        if constexpr (KIND == SHD_LOSS_WL2) {
+          const float ca = in ? (k == 0 ? 1e-8f * coef : coef) : 0.f;
+#pragma unroll
+          for (int nb = 0; nb < 4; ++nb) {
+            const int n = nb * 16 + col;
+            if (nb < NB && n < N) dlw[row * SN + n] = in ? ca * (lg[nb] - (k == n ? tv : -tv)) : 0.f;
+          }
+        } else {
+          const float inv = shd_row_softmax(lg, NB, N);
+          const float ca = (in && k >= 0) ? coef : 0.f;
+#pragma unroll
+          for (int nb = 0; nb < 4; ++nb) {
+            const int n = nb * 16 + col;
+            if (nb < NB && n < N) dlw[row * SN + n] = ca * (lg[nb] * inv - (k == n ? 1.f : 0.f));
+          }
+        }
       }
     }
     __syncthreads();
@@ -2818,6 +3078,45 @@ int synthsr_seg_head_dice_bwd_weighted(const float* probs, const int32_t* seg, c
   hipLaunchKernelGGL(seg_head_dice_bwd_kernel<true>, dim3(syn_grid(nvox, SHD_TILE, head_grid())), dim3(256),
                      ShdBwdLds(C, N, true).total * sizeof(float), (hipStream_t)stream, probs, seg, lut, lut_n, x, nvox, C, N,
                      stats, gamma, beta, eps, w, sums, scale, dbn, dw, db, mask, boundary_weights, class_weights);
+  SYN_CHECK_LAUNCH();
+  return SYNTHSR_OK;
+}
+
+// WeightedL2Loss / CrossEntropyLoss on the logits: no posteriors, sums [3]
+int synthsr_seg_head_logit_loss_fwd(const float* x, int64_t nvox, int C, const float* stats, const float* gamma,
+                                    const float* beta, float eps, const float* w, const float* b, int N, const int32_t* seg,
+                                    const int32_t* lut, int lut_n, int kind, float target_value, float* sums,
+                                    synthsr_stream_t stream) {
+  if (!x || !stats || !gamma || !beta || !w || !b || !seg || !lut || !sums || N < 2 || !shd_ok(nvox, C, N, lut_n, x) ||
+      (kind != SYNTHSR_SEG_LOSS_WL2 && kind != SYNTHSR_SEG_LOSS_CE))
+    return SYNTHSR_EINVAL;
+  const dim3 grid(syn_grid(nvox, SHD_TILE, head_grid()));
+  const size_t lds = ShdFwdLds(C, N, true).total * sizeof(float);
+  if (kind == SYNTHSR_SEG_LOSS_WL2)
+    hipLaunchKernelGGL(seg_head_logit_loss_fwd_kernel<SHD_LOSS_WL2>, grid, dim3(256), lds, (hipStream_t)stream, x, nvox, C, stats,
+                       gamma, beta, eps, w, b, N, seg, lut, lut_n, target_value, sums);
+  else
+    hipLaunchKernelGGL(seg_head_logit_loss_fwd_kernel<SHD_LOSS_CE>, grid, dim3(256), lds, (hipStream_t)stream, x, nvox, C, stats,
+                       gamma, beta, eps, w, b, N, seg, lut, lut_n, target_value, sums);
+  SYN_CHECK_LAUNCH();
+  return SYNTHSR_OK;
+}
+
+int synthsr_seg_head_logit_loss_bwd(const int32_t* seg, const int32_t* lut, int lut_n, const float* x, int64_t nvox, int C, int N,
+                                    const float* stats, const float* gamma, const float* beta, float eps, const float* w,
+                                    const float* b, int kind, float target_value, const float* sums, float scale, float* dbn,
+                                    float* dw, float* db, synthsr_stream_t stream) {
+  if (!seg || !lut || !x || !stats || !gamma || !beta || !w || !b || !sums || !dbn || !dw || !db || N < 2 ||
+      !shd_ok(nvox, C, N, lut_n, x) || (kind != SYNTHSR_SEG_LOSS_WL2 && kind != SYNTHSR_SEG_LOSS_CE))
+    return SYNTHSR_EINVAL;
+  const dim3 grid(syn_grid(nvox, SHD_TILE, head_grid()));
+  const size_t lds = ShdBwdLds(C, N, true).total * sizeof(float);
+  if (kind == SYNTHSR_SEG_LOSS_WL2)
+    hipLaunchKernelGGL(seg_head_logit_loss_bwd_kernel<SHD_LOSS_WL2>, grid, dim3(256), lds, (hipStream_t)stream, seg, lut, lut_n, x,
+                       nvox, C, N, stats, gamma, beta, eps, w, b, target_value, sums, scale, dbn, dw, db);
+  else
+    hipLaunchKernelGGL(seg_head_logit_loss_bwd_kernel<SHD_LOSS_CE>, grid, dim3(256), lds, (hipStream_t)stream, seg, lut, lut_n, x,
+                       nvox, C, N, stats, gamma, beta, eps, w, b, target_value, sums, scale, dbn, dw, db);
   SYN_CHECK_LAUNCH();
   return SYNTHSR_OK;
 }

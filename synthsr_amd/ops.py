@@ -934,6 +934,64 @@ def seg_head_dice_bwd(probs, seg, lut, x, stats, gamma, beta, w, sums, dbn, dw, 
     return dbn
 
 
+SEG_LOGIT_LOSSES = {'wl2': 0, 'ce': 1}   # SYNTHSR_SEG_LOSS_WL2 / _CE
+
+
+def _seg_head_logit_loss_args(what, x, w, b, seg, lut, sums, kind):
+    """shared checks of seg_head_logit_loss_fwd / _bwd: those of the soft-Dice head (without posteriors), three sums and a
+    known loss"""
+    if kind not in SEG_LOGIT_LOSSES:
+        raise ValueError('%s: kind should be \'wl2\' or \'ce\' (got %r)' % (what, kind))
+    if x.dim() != 4:
+        raise ValueError('x should be [d0, d1, d2, C]')
+    C = int(x.shape[-1])
+    nvox = x.numel() // C
+    N = w.numel() // C
+    if w.numel() != C * N or N < 1 or b.numel() != N or seg.numel() != nvox or lut.numel() < 1:
+        raise ValueError('%s: head [%d, %d] with a bias of %d and a label map of %d values do not fit %d voxels'
+                         % (what, C, N, b.numel(), seg.numel(), nvox))
+    if any(t.dtype != torch.float32 for t in (x, w, b, sums)):
+        raise ValueError('%s is fp32 only (x is %s)' % (what, x.dtype))
+    if seg.dtype != torch.int32 or lut.dtype != torch.int32:
+        raise ValueError('%s takes the label map and the lookup table as int32 (got %s, %s)' % (what, seg.dtype, lut.dtype))
+    if sums.numel() != 3:
+        raise ValueError('%s: sums should hold 3 values, holds %d' % (what, sums.numel()))
+    return C, nvox, N
+
+
+def seg_head_logit_loss_fwd(x, stats, gamma, beta, w, b, seg, lut, sums, kind, target_value=5., eps=BN_EPS):
+    """trainable softmax head + a loss on its LOGITS z = bn(x) @ w + b, forward: sums [3] (zeroed here) accumulated, nothing
+    written per voxel.  gt = one-hot of lut[seg] (label values outside the table or mapped to -1: no class).
+    kind 'wl2' (WeightedL2Loss, ext/lab2im/layers.py:1408-1412): sums = sum_v a_v sum_n (z - t (2 gt - 1))^2 | voxels not of
+    class 0 | voxels of class 0, a_v = 1e-8 on class 0 and 1 elsewhere, t = target_value;
+    loss = sums[0] / ((sums[1] + 1e-8 sums[2]) N).
+    kind 'ce' (CrossEntropyLoss, :1498-1526, enable_checks=False): sums = sum of -log softmax(z)_k over the voxels with a
+    class | their number | unused; loss = sums[0] / nvox.  x [d0,d1,d2,C] with C <= 64, 2 <= N <= 64."""
+    C, nvox, N = _seg_head_logit_loss_args('seg_head_logit_loss_fwd', x, w, b, seg, lut, sums, kind)
+    sums.zero_()
+    _lib.check(_L().synthsr_seg_head_logit_loss_fwd(_lib.ptr(x), nvox, C, _lib.ptr(stats), _lib.ptr(gamma), _lib.ptr(beta), eps,
+                                                    _lib.ptr(w), _lib.ptr(b), N, _lib.ptr(seg), _lib.ptr(lut), int(lut.numel()),
+                                                    SEG_LOGIT_LOSSES[kind], float(target_value), _lib.ptr(sums), _lib.stream()),
+               'seg_head_logit_loss_fwd')
+    return sums
+
+
+def seg_head_logit_loss_bwd(seg, lut, x, stats, gamma, beta, w, b, sums, dbn, dw, db, kind, target_value=5., scale=1.0,
+                            eps=BN_EPS):
+    """backward of scale * (the loss of seg_head_logit_loss_fwd) through the head: dbn [d0,d1,d2,C] (gradient w.r.t. the last
+    BatchNorm's output) written, dw [C, N] and db [N] accumulated; sums as seg_head_logit_loss_fwd left them.  x is read once
+    and the logits are formed again: no posteriors are kept between the two calls"""
+    C, nvox, N = _seg_head_logit_loss_args('seg_head_logit_loss_bwd', x, w, b, seg, lut, sums, kind)
+    if dbn.numel() != x.numel() or dw.numel() != C * N or db.numel() != N or any(t.dtype != torch.float32 for t in (dbn, dw, db)):
+        raise ValueError('seg_head_logit_loss_bwd: dbn like x, dw [C, N] and db [N] (float32) are needed')
+    _lib.check(_L().synthsr_seg_head_logit_loss_bwd(_lib.ptr(seg), _lib.ptr(lut), int(lut.numel()), _lib.ptr(x), nvox, C, N,
+                                                    _lib.ptr(stats), _lib.ptr(gamma), _lib.ptr(beta), eps, _lib.ptr(w),
+                                                    _lib.ptr(b), SEG_LOGIT_LOSSES[kind], float(target_value), _lib.ptr(sums),
+                                                    float(scale), _lib.ptr(dbn), _lib.ptr(dw), _lib.ptr(db), _lib.stream()),
+               'seg_head_logit_loss_bwd')
+    return dbn
+
+
 def _seg_head_label_args(what, x, w, b, labels, out):
     """shared checks of seg_head_argmax / _tta_argmax: float32 or bfloat16 activations, a float32 head, int32 label values
     and label map"""

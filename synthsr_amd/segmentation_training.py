@@ -1,14 +1,18 @@
 """`training_segmentation()` — trains the softmax-headed segmentation U-Net that `training(segmentation_model_file=...)`
 freezes behind its prediction (SynthSR/training.py:371-409), with the soft Dice of `DiceLoss` (ext/lab2im/layers.py:1343-1376,
-enable_checks=False) against the generator's own label map.
+enable_checks=False) against the generator's own label map -- or with the two other losses the reference defines for such a
+network: `WeightedL2Loss` on the logits (:1408-1412) for the first `wl2_epochs` epochs, the warm-up that gets a random head past
+the flat start of the Dice, and `CrossEntropyLoss` (:1498-1526, unweighted) in place of the Dice.
 
     per step:  host input sampler -> generator kernels -> U-Net forward on the generator's regression TARGET (what the frozen
-               regulariser will later be fed: a clean one-channel image) -> fused head + softmax + Dice (UNet3D.loss_dice)
+               regulariser will later be fed: a clean one-channel image) -> fused head + loss (UNet3D.loss_dice, or
+               loss_wl2 / loss_cross_entropy, which keep no posteriors)
                -> backward -> Keras-semantics Adam.
 
 The head's channel order is `segmentation_label_list`, the array `training(segmentation_label_list=...)` takes: a checkpoint
 written here plugs straight in.  Generator, step, optimizer, logs and checkpoints are those of synthsr_amd.training.
-Scope: fp32, one process, batchsize 1; everything else raises.
+Scope: fp32, one process, batchsize 1, losses dice | cross_entropy (unweighted) after an optional weighted-L2 warm-up;
+everything else raises.
 """
 import os
 import numpy as np
@@ -36,20 +40,82 @@ def segmentation_lut(segmentation_label_list):
     return lut
 
 
-class SegmentationTrainer(Trainer):
-    """generator + softmax-headed U-Net + soft Dice + Adam; the sample, the optimizer step and the moving statistics are
-    Trainer's"""
+SEGMENTATION_LOSSES = ('dice', 'cross_entropy')
 
-    def __init__(self, brain_generator, net, lut, lr=1e-4, lr_decay=0.0, fixed_sample=False, dice=None):
+
+def phase_loss(epoch, wl2_epochs=0, segmentation_loss='dice'):
+    """the loss of the epoch with 0-based index `epoch`: 'wl2' during the warm-up, then `segmentation_loss`"""
+    return 'wl2' if epoch < wl2_epochs else segmentation_loss
+
+
+def phase_resets_optimizer(epoch, wl2_epochs=0):
+    """whether the optimizer starts afresh (Adam moments and iteration count zeroed) in front of the first step of the epoch
+    with 0-based index `epoch`: at the first epoch behind a warm-up, reached by training through it or by resuming there.  The
+    weighted-L2 gradients are orders of magnitude larger than the Dice's and stale second moments would throttle the first
+    Dice steps (the workflow this mirrors compiles the model anew between the phases)"""
+    return wl2_epochs > 0 and epoch == wl2_epochs
+
+
+def loss_settings(wl2_epochs=0, wl2_target_value=5., segmentation_loss='dice', dice_class_weights=None,
+                  dice_boundary_weights=0., dice_boundary_dist=3, dice_skip_background=True):
+    """the three loss keywords of training_segmentation, checked: (wl2_epochs, wl2_target_value) as (int, float)"""
+    if isinstance(wl2_epochs, bool) or not isinstance(wl2_epochs, (int, np.integer)) or wl2_epochs < 0:
+        raise ValueError('wl2_epochs should be an integer >= 0 (got %r)' % (wl2_epochs,))
+    if isinstance(wl2_target_value, bool) or not isinstance(wl2_target_value, (int, float, np.integer, np.floating)) \
+            or not np.isfinite(wl2_target_value) or not wl2_target_value > 0:
+        raise ValueError('wl2_target_value should be a finite number > 0 (got %r)' % (wl2_target_value,))
+    if segmentation_loss not in SEGMENTATION_LOSSES:
+        raise ValueError('segmentation_loss should be one of %s (got %r)' % (', '.join(map(repr, SEGMENTATION_LOSSES)),
+                                                                            segmentation_loss))
+    if segmentation_loss == 'cross_entropy':
+        at_default = dict(dice_class_weights=dice_class_weights is None,
+                          dice_boundary_weights=np.ndim(dice_boundary_weights) == 0 and dice_boundary_weights == 0,
+                          dice_boundary_dist=np.ndim(dice_boundary_dist) == 0 and dice_boundary_dist == 3,
+                          dice_skip_background=dice_skip_background is True)
+        values = dict(dice_class_weights=dice_class_weights, dice_boundary_weights=dice_boundary_weights,
+                      dice_boundary_dist=dice_boundary_dist, dice_skip_background=dice_skip_background)
+        for name, value in values.items():
+            if not at_default[name]:
+                raise ValueError('segmentation_loss=\'cross_entropy\' is the unweighted cross-entropy: %s=%r is a setting of '
+                                 'the Dice (the reference\'s class-weighted cross-entropy sums over the wrong axis and is not '
+                                 'restated)' % (name, value))
+    return int(wl2_epochs), float(wl2_target_value)
+
+
+class SegmentationTrainer(Trainer):
+    """generator + softmax-headed U-Net + soft Dice (or cross-entropy, behind an optional weighted-L2 warm-up) + Adam; the
+    sample, the optimizer step and the moving statistics are Trainer's"""
+
+    def __init__(self, brain_generator, net, lut, lr=1e-4, lr_decay=0.0, fixed_sample=False, dice=None, wl2_epochs=0,
+                 wl2_target_value=5., segmentation_loss='dice', init_epoch=0, steps_per_epoch=1):
         import torch
         Trainer.__init__(self, brain_generator, net, lr, lr_decay)
         self.lut = torch.as_tensor(np.asarray(lut, dtype=np.int32)).to(net.device)
         self.fixed_sample = bool(fixed_sample)
         self.dice = dict(dice or {})   # the weights of UNet3D.loss_dice (dice_settings); empty: the plain soft Dice
         self._fixed = None
+        self.wl2_epochs, self.wl2_target_value, self.segmentation_loss = int(wl2_epochs), float(wl2_target_value), segmentation_loss
+        self.init_epoch, self.steps_per_epoch = int(init_epoch), int(steps_per_epoch)
+        self.steps_done = 0   # steps of this trainer: with init_epoch and steps_per_epoch, the epoch a step belongs to
+
+    def _loss(self, x, seg):
+        """forward + the loss of the epoch this step belongs to; in front of the first step behind the warm-up the optimizer
+        starts afresh (phase_resets_optimizer)"""
+        net = self.net
+        epoch = self.init_epoch + self.steps_done // self.steps_per_epoch
+        if self.steps_done % self.steps_per_epoch == 0 and phase_resets_optimizer(epoch, self.wl2_epochs):
+            net.adam_m.zero_()
+            net.adam_v.zero_()
+            net.iterations = 0
+        kind = phase_loss(epoch, self.wl2_epochs, self.segmentation_loss)
+        if kind == 'wl2':
+            return net.loss_wl2(x, seg, self.lut, self.wl2_target_value)
+        if kind == 'cross_entropy':
+            return net.loss_cross_entropy(x, seg, self.lut)
+        return net.loss_dice(x, seg, self.lut, **self.dice)
 
     def step(self, model_inputs=None, draws=None, label_index=None):
-        """one training step; returns the Dice loss as a 1-element device tensor (no host sync)"""
+        """one training step; returns the loss as a 1-element device tensor (no host sync)"""
         from . import ops
         net = self.net
         if self._fixed is not None:
@@ -66,12 +132,13 @@ class SegmentationTrainer(Trainer):
                 self._fixed = x, seg = target.clone(), seg.clone()
         net.set_batch(1)
         with ops.trace_range('forward + loss'):
-            loss = net.loss_dice(x, seg, self.lut, **self.dice)
+            loss = self._loss(x, seg)
         with ops.trace_range('backward'):
             net.backward()
         with ops.trace_range('optimizer'):
             net.adam_step(self.lr, self.lr_decay)
             net.update_moving_stats()
+        self.steps_done += 1
         return loss
 
 
@@ -125,7 +192,8 @@ def training_segmentation(labels_dir, model_dir, prior_means, prior_stds, path_g
                           feat_multiplier=2, dropout=0, activation='elu', lr=1e-4, lr_decay=0, epochs=100,
                           steps_per_epoch=1000, checkpoint=None, seed=0, verbose=True, dtype='f32', deterministic=False,
                           fs_header_segnet=False, fixed_sample=False, step_losses=None, dice_class_weights=None,
-                          dice_boundary_weights=0., dice_boundary_dist=3, dice_skip_background=True):
+                          dice_boundary_weights=0., dice_boundary_dist=3, dice_skip_background=True, wl2_epochs=0,
+                          wl2_target_value=5., segmentation_loss='dice'):
     """Generator arguments: those of synthsr_amd.training.training, same names and defaults.  `segmentation_label_list`
     (array or path): the label values the network predicts, in head-channel order; label values of the maps that are not
     listed have no class (an all-zero ground-truth row).  `output_channel`: ONE index, the synthetic channel the network is
@@ -136,8 +204,15 @@ def training_segmentation(labels_dir, model_dir, prior_means, prior_stds, path_g
     the inverse of each label's volume in the sample; a label that the sample does not hold gets weight 0 where the reference
     divides by zero), a sequence or the path of a .npy with one value >= 0 per entry of segmentation_label_list;
     `dice_boundary_weights` (bonus weight of voxels within `dice_boundary_dist`, 1 .. 5, of a label's boundary) and
-    `dice_skip_background` (no bonus for the first label of the list).  Returns the network."""
+    `dice_skip_background` (no bonus for the first label of the list).
+    `wl2_epochs`: the epochs with 0-based index < wl2_epochs (counted from the start of the whole run, not from a resumed
+    checkpoint) train with WeightedL2Loss on the logits (UNet3D.loss_wl2, `wl2_target_value`), the others with
+    `segmentation_loss`: 'dice' or 'cross_entropy' (UNet3D.loss_cross_entropy: unweighted, every dice_* setting at its
+    default).  In front of the first step of epoch index wl2_epochs, trained up to or resumed at, the Adam moments and the
+    iteration count are zeroed; resuming at a later epoch resets nothing.  Returns the network."""
     check_scope(batchsize, dtype, images_dir, fs_header_segnet, int(os.environ.get('WORLD_SIZE', '1')))
+    wl2_epochs, wl2_target_value = loss_settings(wl2_epochs, wl2_target_value, segmentation_loss, dice_class_weights,
+                                                 dice_boundary_weights, dice_boundary_dist, dice_skip_background)
     if deterministic:  # process-wide switch: on for the duration of this call, previous setting restored on the way out
         from . import ops as _ops
         kw = dict(locals())
@@ -191,7 +266,9 @@ def training_segmentation(labels_dir, model_dir, prior_means, prior_stds, path_g
             init_epoch = int(os.path.basename(checkpoint)[:3])
         except ValueError:
             init_epoch = 0
-    trainer = SegmentationTrainer(brain_generator, net, lut, lr, lr_decay, fixed_sample=fixed_sample, dice=dice)
+    trainer = SegmentationTrainer(brain_generator, net, lut, lr, lr_decay, fixed_sample=fixed_sample, dice=dice,
+                                  wl2_epochs=wl2_epochs, wl2_target_value=wl2_target_value, segmentation_loss=segmentation_loss,
+                                  init_epoch=init_epoch, steps_per_epoch=steps_per_epoch)
     step = trainer.step
     if step_losses is not None:
         def step():

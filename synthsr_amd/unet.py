@@ -738,6 +738,7 @@ class UNet3D:
         if self.batch != 1:
             raise NotImplementedError('the soft-Dice training head takes one volume per step (batch = %d)' % self.batch)
         N = self.nb_labels
+        self._logit_loss = None   # backward() follows the last loss call
         self.training = True
         self.frozen_batch_stats = False
         low, bn = self.forward(x)
@@ -779,6 +780,55 @@ class UNet3D:
         torch.sum(c * (1.0 - (sums[:N] + 1e-7) / (sums[N:2 * N] + 1e-7)), 0, keepdim=True, out=self.loss_buf)
         return self.loss_buf
 
+    def _loss_on_logits(self, what, kind, x, seg, lut, target_value):
+        """forward in training mode + ops.seg_head_logit_loss_fwd; keeps (kind, target_value, sums, seg, lut) for backward()"""
+        if self.final_pred_activation != 'softmax':
+            raise ValueError('%s() is for softmax heads; use loss() for a linear head' % what)
+        if self.bf16:
+            raise NotImplementedError('the %s training head is fp32 only (dtype=%r)' % (what, 'bf16'))
+        if self.batch != 1:
+            raise NotImplementedError('the %s training head takes one volume per step (batch = %d)' % (what, self.batch))
+        self._dice = None   # backward() follows the last loss call
+        self._logit_loss = None
+        self.training = True
+        self.frozen_batch_stats = False
+        low, bn = self.forward(x)
+        nvox = low.numel() // low.shape[3]
+        if seg.numel() != nvox:
+            raise ValueError('label map of %d voxels for a prediction of %d' % (seg.numel(), nvox))
+        sums = self.buf('logit_loss_sums', [3])
+        seg = seg.reshape(-1)
+        self.loss_buf = self.buf('loss', [1])
+        ops.seg_head_logit_loss_fwd(low, self._stats(bn), self.view(bn['gamma']), self.view(bn['beta']), self.view(self.head['w']),
+                                    self.view(self.head['b']), seg, lut, sums, kind, target_value)
+        self._logit_loss = (kind, target_value, sums, seg, lut)
+        if kind == 'wl2':
+            torch.div(sums[0:1], (sums[1:2] + 1e-8 * sums[2:3]) * float(self.nb_labels), out=self.loss_buf)
+        else:
+            torch.div(sums[0:1], float(nvox), out=self.loss_buf)
+        return self.loss_buf
+
+    def loss_wl2(self, x, seg, lut, target_value=5.):
+        """training step of a softmax-headed network with WeightedL2Loss (ext/lab2im/layers.py:1408-1412) on the LOGITS, the
+        layer before the softmax: they are pulled towards +target_value where the ground truth is 1 and -target_value where it
+        is 0, voxels of head channel 0 (the background) weigh 1e-8, every other voxel 1 -- the warm-up such networks are
+        started with before the Dice takes over.  x, seg, lut as loss_dice; a voxel without a class has target -target_value
+        in every channel.  Returns the loss as a 1-element device tensor; three sums and the label map are kept for
+        backward().  fp32, batch 1."""
+        if self.final_pred_activation != 'softmax':
+            raise ValueError('loss_wl2() is for softmax heads; use loss() for a linear head')
+        if isinstance(target_value, bool) or not isinstance(target_value, (int, float, np.integer, np.floating)) \
+                or not np.isfinite(target_value) or not target_value > 0:
+            raise ValueError('target_value should be a finite number > 0 (got %r)' % (target_value,))
+        return self._loss_on_logits('loss_wl2', 'wl2', x, seg, lut, float(target_value))
+
+    def loss_cross_entropy(self, x, seg, lut):
+        """training step of a softmax-headed network with CrossEntropyLoss (ext/lab2im/layers.py:1498-1526, enable_checks=False,
+        no weights): the mean over ALL voxels of -log p_k(v), voxels without a class contributing 0.  The logarithm is taken
+        as a log-softmax of the logits: where a posterior underflows in fp32 the reference's log gives inf, this stays finite.
+        x, seg, lut as loss_dice.  Returns the loss as a 1-element device tensor.  fp32, batch 1."""
+        return self._loss_on_logits('loss_cross_entropy', 'ce', x, seg, lut, 0.)
+
     def predict(self, x):
         """inference forward (moving statistics): x [d0,d1,d2,Cin] -> [d0,d1,d2,K] (K = head channels: one per
         regression target; intensities then spreads for a laplace head)"""
@@ -815,7 +865,7 @@ class UNet3D:
         for backward_input).  batch_stats: BatchNorm normalises with the statistics of x's own activations (a frozen Keras
         network inside a model that is being fitted) instead of the moving averages; nothing is updated either way"""
         assert self.nb_labels > 1
-        self._dice = None   # backward() trains only after loss_dice(); this forward is for backward_input()
+        self._dice = self._logit_loss = None   # backward() trains only after a loss call; this forward is for backward_input()
         self.frozen_batch_stats = bool(batch_stats)
         if batch_stats:
             # Keras' learning phase: the forward pass gathers the batch statistics (conv epilogues / bn_stats) and the
@@ -849,7 +899,7 @@ class UNet3D:
         if want_probs and prev is None:
             raise ValueError('predict_labels() forms posteriors only when averaging with prev; use predict_probs()')
         N = self.nb_labels
-        self._dice = None   # the kept activations are overwritten: backward() needs a new loss_dice()
+        self._dice = self._logit_loss = None   # the kept activations are overwritten: backward() needs a new loss call
         was = self.training
         self.training = False
         self.frozen_batch_stats = False
@@ -928,6 +978,14 @@ class UNet3D:
                 self._frozen_sums = torch.zeros_like(self._zero_sums)
             return self._backward_body(g_last, on_grad_ready)
         G.zero_()
+        if self.final_pred_activation == 'softmax' and getattr(self, '_logit_loss', None) is not None:
+            # trained on the logits (loss_wl2 / loss_cross_entropy): the head kernel forms them again from the kept feature map
+            kind, target_value, sums, seg, lut = self._logit_loss
+            dbn = self.buf('dbn_head', list(low.shape))
+            ops.seg_head_logit_loss_bwd(seg, lut, low, self._stats(bn), self.view(bn['gamma']), self.view(bn['beta']),
+                                        self.view(self.head['w']), self.view(self.head['b']), sums, dbn,
+                                        self.view(self.head['w'], G), self.view(self.head['b'], G), kind, target_value)
+            return self._backward_body(dbn, on_grad_ready)
         if self.final_pred_activation == 'softmax':  # trained with the soft Dice (loss_dice): through softmax and head in one pass
             if getattr(self, '_dice', None) is None:
                 raise RuntimeError('backward() on a softmax head needs loss_dice() first (after predict_probs() the network '

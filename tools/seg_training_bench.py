@@ -5,7 +5,9 @@ HBM traffic, and of one segmentation training step next to the regression step o
     python tools/seg_training_bench.py [--size 160] [--C 24] [--N 33] > profiles/seg_training_kernels.txt
 
 With --dice_class_weights -1 and / or --dice_boundary_weights B the weighted forms are timed (and the boundary-mask kernel, on a
-label map of 8^3-voxel blocks: per-voxel random labels put every class into every window, which no anatomy does)."""
+label map of 8^3-voxel blocks: per-voxel random labels put every class into every window, which no anatomy does).
+With --loss wl2 | ce the two kernels of the losses on the logits (synthsr_seg_head_logit_loss_fwd / _bwd: no posteriors, so
+4 nvox (C + 1) bytes forward and 4 nvox (2 C + 1) backward) and a training step with that loss are timed instead."""
 import argparse
 import os
 import sys
@@ -45,6 +47,7 @@ def main():
     ap.add_argument('--dice_boundary_weights', type=float, default=0.)
     ap.add_argument('--dice_boundary_dist', type=int, default=3)
     ap.add_argument('--dice_no_skip_background', dest='dice_skip_background', action='store_false')
+    ap.add_argument('--loss', type=str, default='dice', choices=('dice', 'wl2', 'ce'))
     a = ap.parse_args()
     from synthsr_amd.segmentation_training import dice_settings
     dice = dice_settings(a.N, a.dice_class_weights, a.dice_boundary_weights, a.dice_boundary_dist, a.dice_skip_background)
@@ -68,6 +71,22 @@ def main():
             mask = torch.empty(nvox, dtype=torch.int64).cuda()
         kw_w = dict(mask=mask, boundary_weights=dice['boundary_weights'], class_weights=cw)
     dbn, dw, db = torch.empty_like(x), torch.zeros(C, N).cuda(), torch.zeros(N).cuda()
+    if a.loss != 'dice':
+        if weighted:
+            ap.error('--loss %s has no weights' % a.loss)
+        del probs
+        name = {'wl2': 'weighted-L2', 'ce': 'cross-entropy'}[a.loss]
+        print('%s head kernels (on the logits), %d^3 voxels, C = %d, N = %d, fp32 (median / min / max of 20 launches, HIP events)'
+              % (name, S, C, N))
+        sums3 = torch.empty(3).cuda()
+        rows = [('seg_head_%s_fwd' % a.loss, lambda: ops.seg_head_logit_loss_fwd(x, stats, gamma, beta, w, b, seg, lut, sums3, a.loss),
+                 nvox * 4 * (C + 1)),            # x + label map read
+                ('seg_head_%s_bwd' % a.loss, lambda: ops.seg_head_logit_loss_bwd(seg, lut, x, stats, gamma, beta, w, b, sums3, dbn, dw,
+                                                                                 db, a.loss), nvox * 4 * (2 * C + 1))]   # + dbn written
+        report(rows)
+        del x, dbn
+        steps(a, g, seg, lut, name)
+        return
     print('soft-Dice head kernels, %d^3 voxels, C = %d, N = %d, fp32 (median / min / max of 20 launches, HIP events)' % (S, C, N))
     fwd_bytes = nvox * 4 * (C + 1 + N)           # x + label map read, probs written
     bwd_bytes = nvox * 4 * (N + 1 + C + C)       # probs + label map + x read, dbn written
@@ -86,12 +105,22 @@ def main():
         print('weighted soft Dice: class weights %s, boundary weights %g within %d voxels' % (
             'dynamic' if dice['class_weights'] == -1 else ('fixed' if dice['class_weights'] is not None else 'none'),
             dice['boundary_weights'], dice['boundary_dist']))
+    report(rows)
+    del x, probs, dbn
+    steps(a, g, seg, lut, 'soft Dice', dice)
+
+
+def report(rows):
     for name, fn, nbytes in rows:
         med, lo, hi = timed(fn)
         floor = nbytes / HBM * 1e3
         print('%-18s %.3f ms (%.3f .. %.3f)   compulsory %.1f MB = %.3f ms at 8 TB/s   -> %.0f %% of the HBM floor rate'
               % (name, med, lo, hi, nbytes / 1e6, floor, 100 * floor / med))
-    del x, probs, dbn
+
+
+def steps(a, g, seg, lut, loss_name, dice=None):
+    S, C, N = a.size, a.C, a.N
+    nvox = S ** 3
     torch.cuda.empty_cache()
     kw = dict(feat_mult=2, nb_conv_per_level=2, batch_norm=-1)
     img = torch.rand(S, S, S, 1, generator=g).cuda()
@@ -100,7 +129,12 @@ def main():
     regnet = UNet3D(C, [S, S, S, 1], a.levels, 3, 1, final_pred_activation='linear', **kw)
 
     def seg_step():
-        segnet.loss_dice(img, seg, lut, **dice)
+        if a.loss == 'wl2':
+            segnet.loss_wl2(img, seg, lut)
+        elif a.loss == 'ce':
+            segnet.loss_cross_entropy(img, seg, lut)
+        else:
+            segnet.loss_dice(img, seg, lut, **dice)
         segnet.backward()
         segnet.adam_step(1e-4)
         segnet.update_moving_stats()
@@ -111,7 +145,7 @@ def main():
         regnet.adam_step(1e-4)
         regnet.update_moving_stats()
     print('one training step of UNet3D(%d, %d^3 x 1, %d levels), forward + loss + backward + Adam (median / min / max of 10)' % (C, S, a.levels))
-    for name, fn in (('regression step (1-channel l1 head)', reg_step), ('segmentation step (%d-class soft Dice)' % N, seg_step)):
+    for name, fn in (('regression step (1-channel l1 head)', reg_step), ('segmentation step (%d-class %s)' % (N, loss_name), seg_step)):
         med, lo, hi = timed(fn, warm=3, reps=10)
         print('%-40s %.2f ms (%.2f .. %.2f)' % (name, med, lo, hi))
 
