@@ -763,6 +763,36 @@ int synthsr_seg_resample_argmax(const float* probs, const int* src_shape, int N,
                                 const int* out_shape, const int32_t* labels, int32_t fill_value, int32_t* out, float* probs_out,
                                 synthsr_stream_t stream);
 
+/* --- image-quality sums of a super-resolved volume against its ground truth -----------------------------------------------
+ * pred, truth [shape[0]][shape[1]][shape[2]] fp32, contiguous; mask NULL (every voxel counts) or int32 of the same shape (a voxel
+ * counts where mask != 0).  Results are doubles in DEVICE memory (out), complete when the stream reaches the end of the call.
+ * Every reduction is one record per workgroup in the workspace, added up in slot order in fp64: no float atomics, nothing
+ * allocated, no state, the same bits run after run (deterministic mode has nothing to switch).
+ * workspace: synthsr_sr_scores_workspace_bytes bytes of device memory for any of the three calls, 8-byte aligned, owned by
+ *   the caller; its contents need no initialisation and mean nothing afterwards.
+ * sr_moments: out [12] = n, shift_p, shift_t, S p', S t', S p'^2, S t'^2, S p' t', min p, max p, min t, max t over the masked
+ *   voxels, with p' = pred - shift_p and t' = truth - shift_t: the sums are taken of SHIFTED values (the shift is a masked voxel's
+ *   value), so a volume that is a large offset plus a small signal keeps its variance.  n = 0: sums and shifts 0, min +inf,
+ *   max -inf.
+ * sr_errors: with d = a pred + b - truth, out [4] = n, S |d|, S d^2, max |d| (0 for n = 0).
+ * sr_ssim3d: x = (a pred + b) inv_range, y = truth inv_range; w the 11 x 11 x 11 Gaussian window (sigma 1.5, taps normalised
+ *   to sum 1 per axis) at the 'valid' positions, of which there are (shape[i] - 10) per axis; mx = w * x, my = w * y,
+ *   vx = w * x^2 - mx^2, vy = w * y^2 - my^2, vxy = w * (x y) - mx my, C1 = 0.01^2, C2 = 0.03^2,
+ *     S = (2 mx my + C1) (2 vxy + C2) / ((mx^2 + my^2 + C1) (vx + vy + C2)).
+ *   out [2] = S summed over the positions whose CENTRE voxel is in the mask, and their number.  ssim_map: NULL, or
+ *   [shape[0] - 10][shape[1] - 10][shape[2] - 10] fp32, S at every position (mask or not).  One launch over the volumes (and
+ *   one workgroup that adds the records up); no intermediate map is written.
+ * Limits: every side 1 .. 4096 (sr_ssim3d: 11 .. 4096).  A NULL volume, out or workspace, a side outside the limits, a
+ * misaligned or too small workspace return SYNTHSR_EINVAL before any launch and write nothing (workspace_bytes: -1). */
+int64_t synthsr_sr_scores_workspace_bytes(const int* shape);
+int synthsr_sr_moments(const float* pred, const float* truth, const int32_t* mask, const int* shape, double* out, void* workspace,
+                       int64_t workspace_bytes, synthsr_stream_t stream);
+int synthsr_sr_errors(const float* pred, const float* truth, const int32_t* mask, const int* shape, float a, float b, double* out,
+                      void* workspace, int64_t workspace_bytes, synthsr_stream_t stream);
+int synthsr_sr_ssim3d(const float* pred, const float* truth, const int32_t* mask, const int* shape, float a, float b,
+                      float inv_range, double* out, float* ssim_map, void* workspace, int64_t workspace_bytes,
+                      synthsr_stream_t stream);
+
 /* --- a frozen or inference softmax-headed U-Net in bf16 ------------------------------------------------------------------
  * The feature map x [nvox][C] is bf16 (8-byte aligned: one channel quad per vector load); BatchNorm statistics, gamma / beta,
  * the head's fp32 master weights w / b, posteriors, prev and the Dice sums stay fp32, so the arithmetic on a given bf16 x is

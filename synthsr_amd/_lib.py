@@ -162,6 +162,10 @@ SIGNATURES = {
     'synthsr_seg_keep_largest': (c_int, [_P, _P, POINTER(c_int), _P, c_int, c_int, c_int32, _P, _P, _P, c_int64, _S]),
     'synthsr_seg_resample_argmax': (c_int, [_P, POINTER(c_int), c_int, POINTER(c_int), POINTER(c_double), POINTER(c_int), _P,
                                             c_int32, _P, _P, _S]),
+    'synthsr_sr_scores_workspace_bytes': (c_int64, [POINTER(c_int)]),
+    'synthsr_sr_moments': (c_int, [_P, _P, _P, POINTER(c_int), _P, _P, c_int64, _S]),
+    'synthsr_sr_errors': (c_int, [_P, _P, _P, POINTER(c_int), c_float, c_float, _P, _P, c_int64, _S]),
+    'synthsr_sr_ssim3d': (c_int, [_P, _P, _P, POINTER(c_int), c_float, c_float, c_float, _P, _P, _P, c_int64, _S]),
     'synthsr_seg_head_fwd_bf16': (c_int, [_P, c_int64, c_int, _P, _P, _P, c_float, _P, _P, c_int, _P, _S]),
     'synthsr_seg_dice_bwd_bf16': (c_int, [_P, _P, c_int64, c_int, c_int, _P, _P, _P, c_int, _P, c_float, _P, _S]),
     'synthsr_seg_head_argmax_bf16': (c_int, [_P, c_int64, c_int, _P, _P, _P, c_float, _P, _P, c_int, _P, _P, _S]),

@@ -22,7 +22,8 @@ SOURCES = [('generator.hip', ['-ffp-contract=off']),
            ('critic.hip', []),
            ('conv_bf16.hip', []),
            ('conv_split.hip', []),
-           ('conv3d.hip', [])]
+           ('conv3d.hip', []),
+           ('sr_scores.hip', [])]   # last: the objects before it link in the order they always had
 
 
 def _hipcc():

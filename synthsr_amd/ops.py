@@ -1100,6 +1100,72 @@ def seg_surface_dist2(a, b, lut, N, d2_ab=None, d2_ba=None, workspace=None):
     return outs[0], outs[1]
 
 
+SR_SCORES_MAX_SIDE = 4096   # include/synthsr_hip.h: synthsr_sr_moments / _errors / _ssim3d
+SR_SSIM_WINDOW = 11
+
+
+def sr_scores_workspace_bytes(shape):
+    """bytes of device scratch any of sr_moments / sr_errors / sr_ssim3d needs for volumes of `shape`"""
+    if len(shape) != 3 or not all(1 <= int(s) <= SR_SCORES_MAX_SIDE for s in shape):
+        raise ValueError('the image scores take volumes [d0, d1, d2] with sides 1 .. %d (got %s)' % (SR_SCORES_MAX_SIDE, tuple(shape)))
+    return int(_L().synthsr_sr_scores_workspace_bytes(_lib.i3(shape)))
+
+
+def _sr_scores_args(what, pred, truth, mask, workspace, nout, out, min_side=1):
+    for name, t in (('pred', pred), ('truth', truth)):
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            raise ValueError('%s takes %s as a contiguous float32 volume (got %s)' % (what, name, t.dtype))
+    if pred.dim() != 3 or pred.shape != truth.shape:
+        raise ValueError('%s: volumes of shapes %s and %s' % (what, tuple(pred.shape), tuple(truth.shape)))
+    if min(pred.shape) < min_side:
+        raise ValueError('%s needs every side >= %d (got %s)' % (what, min_side, tuple(pred.shape)))
+    if mask is not None and (mask.dtype != torch.int32 or mask.shape != pred.shape or not mask.is_contiguous()):
+        raise ValueError('%s takes the mask as a contiguous int32 volume of the images\' shape' % what)
+    need = sr_scores_workspace_bytes(pred.shape)
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.uint8, device=pred.device)
+    if workspace.dtype != torch.uint8 or workspace.numel() < need or workspace.data_ptr() % 8:
+        raise ValueError('%s: the workspace should be an 8-byte aligned uint8 tensor of at least %d bytes' % (what, need))
+    if out is None:
+        out = torch.empty(nout, dtype=torch.float64, device=pred.device)
+    if out.dtype != torch.float64 or out.numel() != nout:
+        raise ValueError('%s: out should hold %d float64 values' % (what, nout))
+    return workspace, out
+
+
+def sr_moments(pred, truth, mask=None, out=None, workspace=None):
+    """float64 device tensor [12]: n, shift_p, shift_t, and over the masked voxels the sums of p', t', p'^2, t'^2, p't'
+    (p' = pred - shift_p, t' = truth - shift_t), min / max of pred, min / max of truth (include/synthsr_hip.h)"""
+    workspace, out = _sr_scores_args('sr_moments', pred, truth, mask, workspace, 12, out)
+    _lib.check(_L().synthsr_sr_moments(_lib.ptr(pred), _lib.ptr(truth), _lib.ptr(mask), _lib.i3(pred.shape), _lib.ptr(out),
+                                       _lib.ptr(workspace), workspace.numel(), _lib.stream()), 'sr_moments')
+    return out
+
+
+def sr_errors(pred, truth, mask=None, a=1.0, b=0.0, out=None, workspace=None):
+    """float64 device tensor [4]: n, sum |d|, sum d^2, max |d| over the masked voxels, d = a pred + b - truth"""
+    workspace, out = _sr_scores_args('sr_errors', pred, truth, mask, workspace, 4, out)
+    _lib.check(_L().synthsr_sr_errors(_lib.ptr(pred), _lib.ptr(truth), _lib.ptr(mask), _lib.i3(pred.shape), float(a), float(b),
+                                      _lib.ptr(out), _lib.ptr(workspace), workspace.numel(), _lib.stream()), 'sr_errors')
+    return out
+
+
+def sr_ssim3d(pred, truth, mask=None, a=1.0, b=0.0, inv_range=1.0, want_map=False, out=None, ssim_map=None, workspace=None):
+    """(float64 device tensor [2]: the sum of the 3-D SSIM (11^3 Gaussian window, sigma 1.5, 'valid' positions) of
+    (a pred + b) inv_range against truth inv_range over the positions whose centre voxel is in the mask, and their number;
+    the float32 SSIM map [d0 - 10, d1 - 10, d2 - 10] or None)"""
+    workspace, out = _sr_scores_args('sr_ssim3d', pred, truth, mask, workspace, 2, out, min_side=SR_SSIM_WINDOW)
+    mshape = tuple(int(s) - SR_SSIM_WINDOW + 1 for s in pred.shape)
+    if ssim_map is None and want_map:
+        ssim_map = torch.empty(mshape, dtype=torch.float32, device=pred.device)
+    if ssim_map is not None and (ssim_map.dtype != torch.float32 or tuple(ssim_map.shape) != mshape):
+        raise ValueError('sr_ssim3d: the map should be float32 of shape %s' % (mshape,))
+    _lib.check(_L().synthsr_sr_ssim3d(_lib.ptr(pred), _lib.ptr(truth), _lib.ptr(mask), _lib.i3(pred.shape), float(a), float(b),
+                                      float(inv_range), _lib.ptr(out), _lib.ptr(ssim_map), _lib.ptr(workspace),
+                                      workspace.numel(), _lib.stream()), 'sr_ssim3d')
+    return out, ssim_map
+
+
 COMPONENTS_MAX_GROUPS = 64   # include/synthsr_hip.h: synthsr_seg_components
 CONNECTIVITIES = (6, 18, 26)
 
