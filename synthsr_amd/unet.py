@@ -11,11 +11,41 @@ layer names (`unet_conv_downarm_0_0/kernel` ...), so a Keras .h5 maps 1:1 later.
 Batch size 1 per replica (the configuration of every BASELINE config); BN uses batch statistics in
 training and moving statistics in inference, moving averages updated with Keras 2.3.1 semantics.
 """
+import contextlib
+import ctypes
 import math
+from typing import NamedTuple
 import numpy as np
 import torch
 
-from . import ops
+from . import _lib, ops
+
+
+class _LossState(NamedTuple):
+    """what the last loss call keeps for backward(), by `kind`: 'linear' (loss: dpred, head_ab), 'dice' (loss_dice: probs, sums,
+    seg, lut and, for the weighted Dice only, mask / boundary_weights / class_weights) or 'logits' (loss_wl2 /
+    loss_cross_entropy: loss_kind, target_value, sums, seg, lut).  Every loss entry point sets UNet3D._loss_state once, every
+    predict entry point clears it, UNet3D._backward_inner dispatches on `kind`."""
+    kind: str
+    dpred: torch.Tensor = None
+    head_ab: torch.Tensor = None
+    probs: torch.Tensor = None
+    sums: torch.Tensor = None
+    seg: torch.Tensor = None
+    lut: torch.Tensor = None
+    mask: torch.Tensor = None
+    boundary_weights: float = 0.
+    class_weights: torch.Tensor = None
+    loss_kind: str = None
+    target_value: float = None
+
+
+class _PendingBN(NamedTuple):
+    """a BatchNorm backward whose channel sums are known and whose second pass rides in the next activation backward
+    (UNet3D._elu_backward); pooled: the gradient in flight is still the one w.r.t. the max-POOLED tensor"""
+    bn: dict
+    sums: torch.Tensor
+    pooled: bool = False
 
 
 def dice_class_weights(weights, n_labels):
@@ -73,6 +103,17 @@ class UNet3D:
         self._drop_ps = None        # batchsize > 1: conv name -> [B, C] scales, one mask per sample (see _start_dropout_batch)
         self._mult = None
         self._packed_scaled = False
+        # made on first use; only the attributes exist from the start
+        self._jobs = self._jobs_bf16 = None         # pack-job tables of repack() (None: to be rebuilt) ...
+        self._jobs_epoch = None                     # ... and the conv layout epoch the fp32 one was planned under
+        self._drop_host = self._drop_dev = self._drop_event = None  # staging of the dropout factors (_upload_dropout)
+        self._dice_mask = None                      # boundary mask of the weighted Dice
+        self._dice_fixed = (None, None)             # fixed class weights of the weighted Dice: (host tuple, device copy)
+        self._zero_sums = self._frozen_sums = None  # BatchNorm-backward sums of a frozen network (backward_input)
+        self._dwc_zeroed = (None, 0)                # (the 'dwc' scratch buffer, leading elements known to be zero)
+        self._loss_state = None                     # _LossState of the last loss call
+        self._pending_bn = None                     # _PendingBN during backward()
+        self._head_ab = None
         if conv_size != 3:
             raise NotImplementedError('only conv_size=3 is supported')
         if activation not in ('elu', 'relu'):
@@ -233,66 +274,63 @@ class UNet3D:
             for c in d['convs']:
                 yield c
 
-    def _pack_jobs(self):
-        """job table for synthsr_conv3d_pack_all: every packed weight set of the network, one flat destination"""
-        import ctypes
-        from . import _lib
-        lib = _lib.load()
-        jobs, off = [], 0
-
-        def plan(shape, cin_e, cout_e, plain):
-            out = (ctypes.c_int64 * 8)()
-            _lib.check(lib.synthsr_conv3d_plan(ops.conv_ctx_host(), _lib.i3(shape), cin_e, cout_e, int(plain), out), 'conv3d_plan')
-            return [int(v) for v in out]
-
-        def add(c, key, shape, ci_off, cin, mode, up):
-            nonlocal off
-            cin_total, cout = c['cin'], c['cout']
-            cin_e, cout_e = (cout, cin) if mode else (cin, cout)
-            # kind: 1 plain conv, 2 forward parity convs of a folded decoder conv, 0 their data gradient
-            # (the plan's 7th value and the job's 13th field are reserved; the last job field is the co-chunk count, which the
-            # split layouts, nt <= -100, are decoded with)
-            ck, ncc, nt, nchunks, _, _, reserved, per = plan(shape, cin_e, cout_e, ((2 if mode == 0 else 0) if up else 1))
-            w_off = self.offsets[c['w']][0]
-            c[key + '_off'] = (off, per * (8 if up else 1))
-            for p in range(8 if up else 1):
-                jobs.append([w_off, off, per, cin_total, ci_off, cin, cout, mode, ck, ncc, nt, p if up else -1, reserved,
-                             nchunks])
-                off += per
-
+    def _weight_sets(self):
+        """every packed weight set of the network in the order of the flat packed buffers, as (conv, key, shape, ci_off, cin,
+        mode, up): conv[key] holds input channels ci_off .. ci_off + cin of the conv's kernel for the forward (mode 0) or the
+        data-gradient (mode 1) kernels on a `shape` grid; up: the 8 parity sets of a folded decoder conv's up-sampled half"""
         first = True
         for c in self.all_convs():
-            if c.get('fold'):
+            if c.get('fold'):   # skip-channel half at full resolution + the 8 parity sets of the up-sampled half
                 cs, cl = c['cs'], c['cin'] - c['cs']
                 lo_shape = [s // 2 for s in c['shape']]
-                add(c, 'wp_s', c['shape'], 0, cs, 0, False)
-                add(c, 'wpd_s', c['shape'], 0, cs, 1, False)
-                add(c, 'wp_u', lo_shape, cs, cl, 0, True)
-                add(c, 'wpd_u', lo_shape, cs, cl, 1, True)
+                yield c, 'wp_s', c['shape'], 0, cs, 0, False
+                yield c, 'wpd_s', c['shape'], 0, cs, 1, False
+                yield c, 'wp_u', lo_shape, cs, cl, 0, True
+                yield c, 'wpd_u', lo_shape, cs, cl, 1, True
             else:
-                add(c, 'wp', c['shape'], 0, c['cin'], 0, False)
+                yield c, 'wp', c['shape'], 0, c['cin'], 0, False
                 if not first or self.need_input_grad:  # the first layer's input normally has no gradient
-                    add(c, 'wpd', c['shape'], 0, c['cin'], 1, False)
+                    yield c, 'wpd', c['shape'], 0, c['cin'], 1, False
             first = False
-        # zeros: synthsr_conv3d_pack_all never writes the 19 structurally empty slots of a 27-slot parity set
-        self._packed = torch.zeros(off, dtype=torch.float32, device=self.device)
-        self._jobs = torch.tensor(jobs, dtype=torch.int64, device=self.device)
+
+    def _bind_packed(self, flat):
+        """conv[key] = its slice of the flat packed buffer, for every weight set the job table placed"""
         for c in self.all_convs():
             for key in ('wp', 'wpd', 'wp_s', 'wpd_s', 'wp_u', 'wpd_u'):
                 if key + '_off' in c:
                     o, n = c[key + '_off']
-                    c[key] = self._packed[o:o + n]
+                    c[key] = flat[o:o + n]
+
+    def _pack_jobs(self):
+        """job table for synthsr_conv3d_pack_all: every packed weight set of the network, one flat destination"""
+        lib = _lib.load()
+        jobs, off = [], 0
+        plan = (ctypes.c_int64 * 8)()
+        for c, key, shape, ci_off, cin, mode, up in self._weight_sets():
+            cin_e, cout_e = (c['cout'], cin) if mode else (cin, c['cout'])
+            # kind: 1 plain conv, 2 forward parity convs of a folded decoder conv, 0 their data gradient
+            # (the plan's 7th value and the job's 13th field are reserved; the last job field is the co-chunk count, which the
+            # split layouts, nt <= -100, are decoded with)
+            _lib.check(lib.synthsr_conv3d_plan(ops.conv_ctx_host(), _lib.i3(shape), cin_e, cout_e,
+                                               (2 if mode == 0 else 0) if up else 1, plan), 'conv3d_plan')
+            ck, ncc, nt, nchunks, _, _, reserved, per = [int(v) for v in plan]
+            w_off = self.offsets[c['w']][0]
+            c[key + '_off'] = (off, per * (8 if up else 1))
+            for p in range(8 if up else 1):
+                jobs.append([w_off, off, per, c['cin'], ci_off, cin, c['cout'], mode, ck, ncc, nt, p if up else -1, reserved,
+                             nchunks])
+                off += per
+        # zeros: synthsr_conv3d_pack_all never writes the 19 structurally empty slots of a 27-slot parity set
+        self._packed = torch.zeros(off, dtype=torch.float32, device=self.device)
+        self._jobs = torch.tensor(jobs, dtype=torch.int64, device=self.device)
+        self._bind_packed(self._packed)
 
     def _bf16_pack_jobs(self):
         """job table of synthsr_conv3d_bf16_pack_all: bf16 fragment-ordered copies of every conv kernel (forward, and
         data-gradient where a gradient flows on) in one flat buffer"""
-        import ctypes
-        from . import _lib
         lib = _lib.load()
-        jobs, off, first = [], 0, True
-
-        def add(c, key, ci_off, cin, mode, up):
-            nonlocal off
+        jobs, off = [], 0
+        for c, key, _, ci_off, cin, mode, up in self._weight_sets():
             start = off
             for par in (range(8) if up else (-1,)):
                 job = (ctypes.c_int64 * 13)()
@@ -301,30 +339,12 @@ class UNet3D:
                 off += int(job[2])
                 jobs.append([int(v) for v in job])
             c[key + '_off'] = (start, off - start)
-
-        for c in self.all_convs():
-            if c.get('fold'):   # skip-channel half at full resolution + the 8 parity sets of the up-sampled half (conv_bf16.hip)
-                cs, cl = c['cs'], c['cin'] - c['cs']
-                add(c, 'wp_s', 0, cs, 0, False)
-                add(c, 'wpd_s', 0, cs, 1, False)
-                add(c, 'wp_u', cs, cl, 0, True)
-                add(c, 'wpd_u', cs, cl, 1, True)
-            else:
-                add(c, 'wp', 0, c['cin'], 0, False)
-                if not first or self.need_input_grad:  # the first layer's input normally has no gradient
-                    add(c, 'wpd', 0, c['cin'], 1, False)
-            first = False
         self._packed_bf16 = torch.empty(off, dtype=torch.bfloat16, device=self.device)
         self._jobs_bf16 = torch.tensor(jobs, dtype=torch.int64, device=self.device)
-        for c in self.all_convs():
-            for key in ('wp', 'wpd', 'wp_s', 'wpd_s', 'wp_u', 'wpd_u'):
-                if key + '_off' in c:
-                    o, n = c[key + '_off']
-                    c[key] = self._packed_bf16[o:o + n]
+        self._bind_packed(self._packed_bf16)
 
     def _repack_bf16(self, src=None):
-        from . import _lib
-        if getattr(self, '_jobs_bf16', None) is None:
+        if self._jobs_bf16 is None:
             self._bf16_pack_jobs()
         _lib.check(_lib.load().synthsr_conv3d_bf16_pack_all(_lib.ptr(self.params if src is None else src),
                                                             _lib.ptr(self._packed_bf16), _lib.ptr(self._jobs_bf16),
@@ -336,8 +356,7 @@ class UNet3D:
         self._packed_scaled = src is not None
         if self.bf16:
             return self._repack_bf16(src)
-        from . import _lib
-        if getattr(self, '_jobs', None) is None or getattr(self, '_jobs_epoch', None) != ops.conv_layout_epoch():
+        if self._jobs is None or self._jobs_epoch != ops.conv_layout_epoch():
             self._jobs_epoch = ops.conv_layout_epoch()   # the packed layouts depend on the arithmetic / plan options
             self._pack_jobs()
         _lib.check(_lib.load().synthsr_conv3d_pack_all(_lib.ptr(self.params if src is None else src), _lib.ptr(self._packed),
@@ -384,6 +403,26 @@ class UNet3D:
         o, C = bn['soff'], bn['C']
         src = self.bn_batch if (self.training or self.frozen_batch_stats) else self.bn_moving
         return src[o:o + 2 * C]
+
+    def _head_in(self, low, bn):
+        """what every head kernel reads: the last feature map, its BatchNorm (statistics, gamma, beta) and the head's w, b"""
+        return (low, self._stats(bn), self.view(bn['gamma']), self.view(bn['beta']), self.view(self.head['w']),
+                self.view(self.head['b']))
+
+    def _head_grads(self):
+        """(dw, db) of the head, in self.grads"""
+        return self.view(self.head['w'], self.grads), self.view(self.head['b'], self.grads)
+
+    @contextlib.contextmanager
+    def _mode(self, training, batch_stats=False):
+        """`training` / `frozen_batch_stats` for the forward inside; `training` is put back afterwards (frozen_batch_stats
+        stays: backward_input() runs the BatchNorms as that forward did)"""
+        was = self.training
+        self.training, self.frozen_batch_stats = training, batch_stats
+        try:
+            yield
+        finally:
+            self.training = was
 
     # ------------------------------------------------------------------ batches of volumes (SynthSR/training.py: batchsize)
     def set_batch(self, batch):
@@ -434,7 +473,7 @@ class UNet3D:
 
     def _upload_dropout(self, flat):
         n = flat.numel()
-        if getattr(self, '_drop_host', None) is None or self._drop_host.numel() != n:
+        if self._drop_host is None or self._drop_host.numel() != n:
             self._drop_host = torch.empty(n, dtype=torch.float32).pin_memory()  # one pinned staging + one device buffer
             self._drop_dev = torch.empty(n, dtype=torch.float32, device=self.device)
             self._drop_event = None
@@ -521,12 +560,38 @@ class UNet3D:
         inv2 = torch.where(s > 0, 1.0 / (s * s).clamp_min(1e-30), torch.full_like(s, float('inf')))
         var.add_(ops.BN_EPS * (inv2 - 1.0))
 
+    def _level_convs(self, convs, cur, bn, side, idx, l, skip_first, per_sample):
+        """the convolutions of one level (`side` 'enc' | 'dec', its idx-th, on the grid of level l) on `cur`, then the batch
+        statistics of `bn` when training: from the last conv's epilogue (batch 1), else one bn_stats pass over what the
+        BatchNorm reads.  skip_first: the caller ran convs[0] (a folded decoder conv) and `cur` is its output.  per_sample:
+        every conv output y is followed by its dropped-out copy, which the next layer and the BatchNorm read.
+        Returns (what the BatchNorm reads, conv outputs, dropped-out copies)"""
+        acts, dacts, have_stats = [], [], False
+        for k, c in enumerate(convs):
+            if skip_first and k == 0:
+                continue
+            out = self.buf('%s%d_%d' % (side, idx, k), self._bshape(l) + [c['cout']])
+            if self.training and k == len(convs) - 1 and self.batch == 1:  # the BatchNorm statistics ride in the conv epilogue
+                cur = ops.conv3d_stats(cur, c['wp'], self.view(c['b']), c['cout'], self._stats(bn), self.bn_ws, self._act,
+                                       out=out)
+                have_stats = True
+            else:
+                self._pb(lambda x_, o_, c=c: ops.conv3d(x_, c['wp'], self.view(c['b']), c['cout'], self._act, out=o_), cur, out)
+                cur = out
+            acts.append(cur)
+            if per_sample:
+                cur = self._dropped(cur, c, '%sd%d_%d' % (side, idx, k))
+                dacts.append(cur)
+        if self.training and not have_stats:  # a batch, or a level whose only conv was the folded one
+            ops.bn_stats(cur, self._stats(bn), self.bn_ws)
+        return cur, acts, dacts
+
     # ------------------------------------------------------------------ forward
     def forward(self, x):
         """x [d0,d1,d2,Cin] -> saves activations; returns the last decoder activation (pre-BN) and its BN"""
         L = self.nb_levels
         if not self.bf16:   # packed weights of another arithmetic would be read under this one's plans (ADVICE r05)
-            ops.check_layout_epoch(getattr(self, '_jobs_epoch', None), 'UNet3D.forward')
+            ops.check_layout_epoch(self._jobs_epoch, 'UNet3D.forward')
         self.saved = dict(x=[], enc=[], cat=[], dec=[])
         dropping = self.training and self.conv_dropout > 0
         per_sample = dropping and self.batch > 1
@@ -549,27 +614,10 @@ class UNet3D:
         for l in range(L):
             e = self.enc[l]
             self.saved['x'].append(cur)
-            acts = []
-            nconv = len(e['convs'])
-            for k, c in enumerate(e['convs']):
-                out = self.buf('enc%d_%d' % (l, k), self._bshape(l) + [c['cout']])
-                if self.training and k == nconv - 1 and self.batch == 1:  # the BatchNorm statistics ride in the conv epilogue
-                    cur = ops.conv3d_stats(cur, c['wp'], self.view(c['b']), c['cout'], self._stats(e['bn']), self.bn_ws,
-                                           self._act, out=out)
-                else:
-                    self._pb(lambda x_, o_, c=c: ops.conv3d(x_, c['wp'], self.view(c['b']), c['cout'], self._act, out=o_), cur, out)
-                    cur = out
-                    if self.training and k == nconv - 1 and not per_sample:
-                        ops.bn_stats(cur, self._stats(e['bn']), self.bn_ws)
-                acts.append(cur)
-                if per_sample:
-                    cur = self._dropped(cur, c, 'encd%d_%d' % (l, k))
-                    if k == 0:
-                        self.saved['encd'].append([])
-                    self.saved['encd'][l].append(cur)
-                    if k == nconv - 1:
-                        ops.bn_stats(cur, self._stats(e['bn']), self.bn_ws)
+            cur, acts, dacts = self._level_convs(e['convs'], cur, e['bn'], 'enc', l, l, False, per_sample)
             self.saved['enc'].append(acts)
+            if per_sample:
+                self.saved['encd'].append(dacts)
             if dropping:
                 self._dropout_bn(e['bn'], self._drop[e['convs'][-1]['name']])
             if l < L - 1:
@@ -579,7 +627,7 @@ class UNet3D:
         for k, d in enumerate(self.dec):
             l = d['level']
             skip = self.saved['enc'][l][-1]
-            acts, dacts = [], []
+            acts0, dacts0 = [], []
             if d['fold']:
                 c0 = d['convs'][0]
                 lo_bn = ops.bn_apply(low, self._stats(low_bn), self.view(low_bn['gamma']), self.view(low_bn['beta']),
@@ -593,38 +641,20 @@ class UNet3D:
                     ops.conv3d_up(lo_, c0['wp_u'], None, None, c0['cout'], 0, out=o_)
                     ops.conv3d_add(skip_, c0['wp_s'], self.view(c0['b']), o_, c0['cout'], self._act, out=o_)
                 self._pb(folded, lo_bn, skip, cur)
-                acts.append(cur)
+                acts0.append(cur)
                 if per_sample:
                     cur = self._dropped(cur, c0, 'decd%d_0' % k)
-                    dacts.append(cur)
+                    dacts0.append(cur)
             else:
                 cat = ops.upsample_concat(skip, low, self._stats(low_bn), self.view(low_bn['gamma']),
                                           self.view(low_bn['beta']),
                                           out=self.buf('cat%d' % k, self._bshape(l) + [skip.shape[3] + low.shape[3]]))
                 self.saved['cat'].append(cat)
                 cur = cat
-            nconv = len(d['convs'])
-            stats_done = False
-            for j, c in enumerate(d['convs']):
-                if d['fold'] and j == 0:
-                    continue
-                out = self.buf('dec%d_%d' % (k, j), self._bshape(l) + [c['cout']])
-                if self.training and j == nconv - 1 and self.batch == 1:
-                    cur = ops.conv3d_stats(cur, c['wp'], self.view(c['b']), c['cout'], self._stats(d['bn']), self.bn_ws,
-                                           self._act, out=out)
-                    stats_done = True
-                else:
-                    self._pb(lambda x_, o_, c=c: ops.conv3d(x_, c['wp'], self.view(c['b']), c['cout'], self._act, out=o_), cur, out)
-                    cur = out
-                acts.append(cur)
-                if per_sample:
-                    cur = self._dropped(cur, c, 'decd%d_%d' % (k, j))
-                    dacts.append(cur)
-            self.saved['dec'].append(acts)
+            cur, acts, dacts = self._level_convs(d['convs'], cur, d['bn'], 'dec', k, l, d['fold'], per_sample)
+            self.saved['dec'].append(acts0 + acts)
             if per_sample:
-                self.saved['decd'].append(dacts)
-            if self.training and not stats_done:  # single-conv level whose only conv was the folded one (or per-sample dropout)
-                ops.bn_stats(cur, self._stats(d['bn']), self.bn_ws)
+                self.saved['decd'].append(dacts0 + dacts)
             if dropping:
                 self._dropout_bn(d['bn'], self._drop[d['convs'][-1]['name']])
             low, low_bn = cur, d['bn']
@@ -652,7 +682,6 @@ class UNet3D:
         low, bn = self.forward(x)
         nvox = low.numel() // low.shape[3]
         C_last = int(low.shape[3])
-        self._head_ab = None
         crop = None
         if loss_cropping is not None:
             size = [int(loss_cropping)] * 3 if np.ndim(loss_cropping) == 0 else [int(v) for v in loss_cropping]
@@ -664,44 +693,41 @@ class UNet3D:
         self.loss_buf.zero_()
         self.dpred = self.buf('dpred', [nvox * K])
         pred = self.buf('pred', [nvox * K]) if want_pred else None
-        if self.batch > 1 and (kind == 'ssim' or crop is not None):
+        per_volume = self.batch > 1 and (kind == 'ssim' or crop is not None)
+        self._head_ab = None
+        if fuse_head_bwd and not per_volume and self.training and K == 1 and kind in ('l1', 'l2') and C_last <= 120:
+            self._head_ab = self.buf('head_ab', [C_last + 1])
+            self._head_ab.zero_()
+        self._loss_state = _LossState('linear', dpred=self.dpred, head_ab=self._head_ab)
+        head = self._head_in(low, bn)
+        scratch = lambda key, numel: self.buf(key, [numel])
+        if per_volume:
             # a loss defined per volume (the centred loss_cropping box, the slice-wise SSIM windows) on a batch: volume by
             # volume on slices of the stack -- BatchNorm statistics stay those of the whole batch -- then the mean over the
             # batch (the reference's K.mean over [B, ...], metrics_model.py:100-125): loss and gradient times 1 / B
             B, nvb = self.batch, nvox // self.batch
             pred = self.buf('pred', [nvox * K])
-            stats, gam, bet = self._stats(bn), self.view(bn['gamma']), self.view(bn['beta'])
-            hw, hb = self.view(self.head['w']), self.view(self.head['b'])
             for b_, lo_b in enumerate(low.chunk(B, 0)):
                 tgt_b = target.reshape(B, -1)[b_]
                 res_b = None if residual is None else residual.reshape(B, nvb, -1)[b_]
                 pred_b, dpred_b = pred.view(B, nvb * K)[b_], self.dpred.view(B, nvb * K)[b_]
                 if kind == 'ssim':
-                    ops.head_loss_fwd(lo_b, stats, gam, bet, hw, hb, tgt_b, self.buf('loss_unused', [1]), kind='l1', pred=pred_b,
+                    ops.head_loss_fwd(lo_b, *head[1:], tgt_b, self.buf('loss_unused', [1]), kind='l1', pred=pred_b,
                                       residual=res_b, res_stride=res_stride, res_off=res_off)
-                    ops.ssim_loss(pred_b, tgt_b, lo_b.shape[:3], self.loss_buf, dpred_b, crop=crop,
-                                  scratch=lambda key, numel: self.buf(key, [numel]))
+                    ops.ssim_loss(pred_b, tgt_b, lo_b.shape[:3], self.loss_buf, dpred_b, crop=crop, scratch=scratch)
                 else:
-                    ops.head_loss_fwd(lo_b, stats, gam, bet, hw, hb, tgt_b, self.loss_buf, kind=kind, crop=crop, pred=pred_b,
+                    ops.head_loss_fwd(lo_b, *head[1:], tgt_b, self.loss_buf, kind=kind, crop=crop, pred=pred_b,
                                       dpred=dpred_b, residual=res_b, res_stride=res_stride, res_off=res_off)
             self.loss_buf.mul_(1.0 / B)
             self.dpred.mul_(1.0 / B)
-            return self.loss_buf, pred
-        if kind == 'ssim':  # the head kernel only produces the prediction; loss and gradient come from the SSIM kernels
+        elif kind == 'ssim':  # the head kernel only produces the prediction; loss and gradient come from the SSIM kernels
             pred = self.buf('pred', [nvox])
-            ops.head_loss_fwd(low, self._stats(bn), self.view(bn['gamma']), self.view(bn['beta']),
-                              self.view(self.head['w']), self.view(self.head['b']), target, self.buf('loss_unused', [1]),
-                              kind='l1', pred=pred, residual=residual, res_stride=res_stride, res_off=res_off)
-            ops.ssim_loss(pred, target, low.shape[:3], self.loss_buf, self.dpred, crop=crop,
-                          scratch=lambda key, numel: self.buf(key, [numel]))
-            return self.loss_buf, pred
-        self._head_ab = None
-        if fuse_head_bwd and self.training and K == 1 and kind in ('l1', 'l2') and C_last <= 120:
-            self._head_ab = self.buf('head_ab', [C_last + 1])
-            self._head_ab.zero_()
-        ops.head_loss_fwd(low, self._stats(bn), self.view(bn['gamma']), self.view(bn['beta']), self.view(self.head['w']),
-                          self.view(self.head['b']), target, self.loss_buf, kind=kind, crop=crop, pred=pred,
-                          dpred=self.dpred, residual=residual, res_stride=res_stride, res_off=res_off, ab=self._head_ab)
+            ops.head_loss_fwd(*head, target, self.buf('loss_unused', [1]), kind='l1', pred=pred, residual=residual,
+                              res_stride=res_stride, res_off=res_off)
+            ops.ssim_loss(pred, target, low.shape[:3], self.loss_buf, self.dpred, crop=crop, scratch=scratch)
+        else:
+            ops.head_loss_fwd(*head, target, self.loss_buf, kind=kind, crop=crop, pred=pred, dpred=self.dpred,
+                              residual=residual, res_stride=res_stride, res_off=res_off, ab=self._head_ab)
         return self.loss_buf, pred
 
     def loss_l1(self, x, target, residual=None, res_stride=1, res_off=0, want_pred=False):
@@ -723,8 +749,7 @@ class UNet3D:
           boundary_weights  bonus b > 0: voxel v counts 1 + b times in the sums of label n where it lies within
                             boundary_dist (1 .. 5) of label n's boundary (ops.seg_boundary_mask, computed once per call)
           skip_background   no bonus for head channel 0"""
-        if self.final_pred_activation != 'softmax':
-            raise ValueError('loss_dice() is for softmax heads; use loss() for a linear head')
+        self._need_softmax('loss_dice')
         bw = float(boundary_weights)
         if not bw >= 0. or bw == float('inf'):
             raise ValueError('boundary_weights should be a finite number >= 0 (got %r)' % (boundary_weights,))
@@ -733,38 +758,23 @@ class UNet3D:
         dynamic = isinstance(class_weights, (int, float)) and class_weights == -1
         if class_weights is not None and not dynamic:
             class_weights = dice_class_weights(class_weights, self.nb_labels)
-        if self.bf16:
-            raise NotImplementedError('the soft-Dice training head is fp32 only (dtype=%r)' % 'bf16')
-        if self.batch != 1:
-            raise NotImplementedError('the soft-Dice training head takes one volume per step (batch = %d)' % self.batch)
         N = self.nb_labels
-        self._logit_loss = None   # backward() follows the last loss call
-        self.training = True
-        self.frozen_batch_stats = False
-        low, bn = self.forward(x)
-        nvox = low.numel() // low.shape[3]
-        if seg.numel() != nvox:
-            raise ValueError('label map of %d voxels for a prediction of %d' % (seg.numel(), nvox))
+        low, bn, nvox, seg = self._softmax_training_forward('loss_dice', 'soft-Dice', x, seg)
         probs = self.buf('probs', [nvox, N])
-        self.loss_buf = self.buf('loss', [1])
         if class_weights is None and not bw:   # the plain soft Dice: the unweighted kernels
             sums = self.buf('dice_sums', [2 * N])
-            seg = seg.reshape(-1)
-            ops.seg_head_dice_fwd(low, self._stats(bn), self.view(bn['gamma']), self.view(bn['beta']),
-                                  self.view(self.head['w']), self.view(self.head['b']), seg, lut, probs, sums)
-            self._dice = (probs, sums, seg, lut)
+            ops.seg_head_dice_fwd(*self._head_in(low, bn), seg, lut, probs, sums)
+            self._loss_state = _LossState('dice', probs=probs, sums=sums, seg=seg, lut=lut)
             torch.mean(1.0 - (sums[:N] + 1e-7) / (sums[N:] + 1e-7), 0, keepdim=True, out=self.loss_buf)
             return self.loss_buf
         mask = None
         if bw:   # 8 bytes per voxel, written once here and read by the two head kernels
-            if getattr(self, '_dice_mask', None) is None or self._dice_mask.numel() != nvox:
+            if self._dice_mask is None or self._dice_mask.numel() != nvox:
                 self._dice_mask = torch.empty(nvox, dtype=torch.int64, device=self.device)
             mask = ops.seg_boundary_mask(seg.reshape(low.shape[:3]), lut, N, boundary_dist, skip_background,
                                          mask=self._dice_mask)
         sums = self.buf('dice_sums_w', [3 * N])
-        seg = seg.reshape(-1)
-        ops.seg_head_dice_fwd(low, self._stats(bn), self.view(bn['gamma']), self.view(bn['beta']), self.view(self.head['w']),
-                              self.view(self.head['b']), seg, lut, probs, sums, mask=mask, boundary_weights=bw, class_weights=True)
+        ops.seg_head_dice_fwd(*self._head_in(low, bn), seg, lut, probs, sums, mask=mask, boundary_weights=bw, class_weights=True)
         c = self.buf('dice_class_weights', [N])
         if dynamic:   # the inverse of the (weighted) volumes; a label without a voxel: 0.  All on the device
             vol = sums[2 * N:]
@@ -773,35 +783,42 @@ class UNet3D:
         elif class_weights is None:
             c.fill_(1.0 / N)
         else:   # fixed weights: uploaded when they change, not every step
-            if getattr(self, '_dice_fixed', (None, None))[0] != class_weights:
+            if self._dice_fixed[0] != class_weights:
                 self._dice_fixed = (class_weights, torch.tensor(class_weights, dtype=torch.float32, device=self.device))
             c.copy_(self._dice_fixed[1])
-        self._dice = (probs, sums, seg, lut, mask, bw, c)
+        self._loss_state = _LossState('dice', probs=probs, sums=sums, seg=seg, lut=lut, mask=mask, boundary_weights=bw,
+                                      class_weights=c)
         torch.sum(c * (1.0 - (sums[:N] + 1e-7) / (sums[N:2 * N] + 1e-7)), 0, keepdim=True, out=self.loss_buf)
         return self.loss_buf
 
-    def _loss_on_logits(self, what, kind, x, seg, lut, target_value):
-        """forward in training mode + ops.seg_head_logit_loss_fwd; keeps (kind, target_value, sums, seg, lut) for backward()"""
+    def _need_softmax(self, what):
         if self.final_pred_activation != 'softmax':
             raise ValueError('%s() is for softmax heads; use loss() for a linear head' % what)
+
+    def _softmax_training_forward(self, what, head, x, seg):
+        """what the training steps of a softmax head share: their checks (`what`: the entry point, `head`: its name in the
+        messages), training mode on batch statistics, the forward and the label map's size.  Returns the last feature map, its
+        BatchNorm, the voxel count and the flat label map; self.loss_buf is the 1-element loss"""
+        self._need_softmax(what)
         if self.bf16:
-            raise NotImplementedError('the %s training head is fp32 only (dtype=%r)' % (what, 'bf16'))
+            raise NotImplementedError('the %s training head is fp32 only (dtype=%r)' % (head, 'bf16'))
         if self.batch != 1:
-            raise NotImplementedError('the %s training head takes one volume per step (batch = %d)' % (what, self.batch))
-        self._dice = None   # backward() follows the last loss call
-        self._logit_loss = None
+            raise NotImplementedError('the %s training head takes one volume per step (batch = %d)' % (head, self.batch))
         self.training = True
         self.frozen_batch_stats = False
         low, bn = self.forward(x)
         nvox = low.numel() // low.shape[3]
         if seg.numel() != nvox:
             raise ValueError('label map of %d voxels for a prediction of %d' % (seg.numel(), nvox))
-        sums = self.buf('logit_loss_sums', [3])
-        seg = seg.reshape(-1)
         self.loss_buf = self.buf('loss', [1])
-        ops.seg_head_logit_loss_fwd(low, self._stats(bn), self.view(bn['gamma']), self.view(bn['beta']), self.view(self.head['w']),
-                                    self.view(self.head['b']), seg, lut, sums, kind, target_value)
-        self._logit_loss = (kind, target_value, sums, seg, lut)
+        return low, bn, nvox, seg.reshape(-1)
+
+    def _loss_on_logits(self, what, kind, x, seg, lut, target_value):
+        """forward in training mode + ops.seg_head_logit_loss_fwd; keeps (kind, target_value, sums, seg, lut) for backward()"""
+        low, bn, nvox, seg = self._softmax_training_forward(what, what, x, seg)
+        sums = self.buf('logit_loss_sums', [3])
+        ops.seg_head_logit_loss_fwd(*self._head_in(low, bn), seg, lut, sums, kind, target_value)
+        self._loss_state = _LossState('logits', loss_kind=kind, target_value=target_value, sums=sums, seg=seg, lut=lut)
         if kind == 'wl2':
             torch.div(sums[0:1], (sums[1:2] + 1e-8 * sums[2:3]) * float(self.nb_labels), out=self.loss_buf)
         else:
@@ -815,8 +832,7 @@ class UNet3D:
         started with before the Dice takes over.  x, seg, lut as loss_dice; a voxel without a class has target -target_value
         in every channel.  Returns the loss as a 1-element device tensor; three sums and the label map are kept for
         backward().  fp32, batch 1."""
-        if self.final_pred_activation != 'softmax':
-            raise ValueError('loss_wl2() is for softmax heads; use loss() for a linear head')
+        self._need_softmax('loss_wl2')
         if isinstance(target_value, bool) or not isinstance(target_value, (int, float, np.integer, np.floating)) \
                 or not np.isfinite(target_value) or not target_value > 0:
             raise ValueError('target_value should be a finite number > 0 (got %r)' % (target_value,))
@@ -835,9 +851,8 @@ class UNet3D:
         if self.final_pred_activation != 'linear':
             raise ValueError('predict() is for linear heads; use predict_probs() for a softmax head')
         K = self.nb_labels
-        was = self.training
-        self.training = False
-        try:
+        self._loss_state = None   # the kept activations are overwritten: backward() needs a new loss call
+        with self._mode(False, self.frozen_batch_stats):
             low, bn = self.forward(x)
             nvox = low.numel() // low.shape[3]
             zero_t = self.buf('zero_t', [nvox * K])
@@ -845,10 +860,7 @@ class UNet3D:
             loss = self.buf('loss', [1])
             loss.zero_()
             pred = self.buf('pred', [nvox * K])
-            ops.head_loss_fwd(low, self._stats(bn), self.view(bn['gamma']), self.view(bn['beta']),
-                              self.view(self.head['w']), self.view(self.head['b']), zero_t, loss, kind='l1', pred=pred)
-        finally:
-            self.training = was
+            ops.head_loss_fwd(*self._head_in(low, bn), zero_t, loss, kind='l1', pred=pred)
         return pred.view(self.batch * self.input_shape[0], self.input_shape[1], self.input_shape[2], K)
 
     # ------------------------------------------------------------------ frozen use (segmentation network)
@@ -865,24 +877,16 @@ class UNet3D:
         for backward_input).  batch_stats: BatchNorm normalises with the statistics of x's own activations (a frozen Keras
         network inside a model that is being fitted) instead of the moving averages; nothing is updated either way"""
         assert self.nb_labels > 1
-        self._dice = self._logit_loss = None   # backward() trains only after a loss call; this forward is for backward_input()
-        self.frozen_batch_stats = bool(batch_stats)
-        if batch_stats:
-            # Keras' learning phase: the forward pass gathers the batch statistics (conv epilogues / bn_stats) and the
-            # Dropout layers of a network built with conv_dropout > 0 are active, frozen or not (the reference builds its
-            # segmentation unet with conv_dropout=dropout, SynthSR/training.py:381); backward_input sees the same masks
-            self.training = True
-            try:
-                low, bn = self.forward(x)
-            finally:
-                self.training = False
-        else:
-            self.training = False
+        self._loss_state = None   # backward() trains only after a loss call; this forward is for backward_input()
+        self.training = False     # frozen from here on, whatever the network was before
+        # batch_stats = Keras' learning phase: the forward pass gathers the batch statistics (conv epilogues / bn_stats) and the
+        # Dropout layers of a network built with conv_dropout > 0 are active, frozen or not (the reference builds its
+        # segmentation unet with conv_dropout=dropout, SynthSR/training.py:381); backward_input sees the same masks
+        with self._mode(bool(batch_stats), bool(batch_stats)):
             low, bn = self.forward(x)
         nvox = low.numel() // low.shape[3]
         probs = self.buf('probs', [nvox, self.nb_labels])
-        ops.seg_head_fwd(low, self._stats(bn), self.view(bn['gamma']), self.view(bn['beta']), self.view(self.head['w']),
-                         self.view(self.head['b']), probs)
+        ops.seg_head_fwd(*self._head_in(low, bn), probs)
         return probs
 
     def predict_labels(self, x, labels, prev=None, perm=None, want_probs=False):
@@ -899,16 +903,12 @@ class UNet3D:
         if want_probs and prev is None:
             raise ValueError('predict_labels() forms posteriors only when averaging with prev; use predict_probs()')
         N = self.nb_labels
-        self._dice = self._logit_loss = None   # the kept activations are overwritten: backward() needs a new loss call
-        was = self.training
-        self.training = False
-        self.frozen_batch_stats = False
-        try:
+        self._loss_state = None   # the kept activations are overwritten: backward() needs a new loss call
+        with self._mode(False):
             low, bn = self.forward(x)
             nvox = low.numel() // low.shape[3]
             out = self.buf('label_map', [nvox]).view(torch.int32)
-            head = (low, self._stats(bn), self.view(bn['gamma']), self.view(bn['beta']), self.view(self.head['w']),
-                    self.view(self.head['b']), labels)
+            head = self._head_in(low, bn) + (labels,)
             probs = None
             if prev is None:
                 ops.seg_head_argmax(*head, out)
@@ -918,8 +918,6 @@ class UNet3D:
                 if want_probs:
                     probs = self.buf('probs_avg', [nvox, N])
                 ops.seg_head_tta_argmax(*head, prev, perm, out, probs)
-        finally:
-            self.training = was
         out = out.view(*low.shape[:3])
         return (out, probs) if want_probs else out
 
@@ -945,8 +943,7 @@ class UNet3D:
         L = self.nb_levels
         G = self.grads
         if not self.bf16:
-            ops.check_layout_epoch(getattr(self, '_jobs_epoch', None), 'UNet3D.backward')
-        self._frozen = frozen
+            ops.check_layout_epoch(self._jobs_epoch, 'UNet3D.backward')
         self._pending_bn = None
         if ops._deterministic:  # ordered in-workgroup sums need a fixed channel group per thread (unet_pointwise.hip)
             bad = [c for c in set(self.feats) if c % 4 or 384 % (c // 4)]
@@ -969,60 +966,48 @@ class UNet3D:
         return self._backward_inner(on_grad_ready, g_last, frozen)
 
     def _backward_inner(self, on_grad_ready, g_last, frozen):
-        G = self.grads
         low, bn = self.saved['last']
-        C = low.shape[3]
         if frozen:
-            if getattr(self, '_zero_sums', None) is None:
+            if self._zero_sums is None:
                 self._zero_sums = torch.zeros(2 * max(b['C'] for b in self.bn_layers), device=self.device)
                 self._frozen_sums = torch.zeros_like(self._zero_sums)
-            return self._backward_body(g_last, on_grad_ready)
-        G.zero_()
-        if self.final_pred_activation == 'softmax' and getattr(self, '_logit_loss', None) is not None:
-            # trained on the logits (loss_wl2 / loss_cross_entropy): the head kernel forms them again from the kept feature map
-            kind, target_value, sums, seg, lut = self._logit_loss
-            dbn = self.buf('dbn_head', list(low.shape))
-            ops.seg_head_logit_loss_bwd(seg, lut, low, self._stats(bn), self.view(bn['gamma']), self.view(bn['beta']),
-                                        self.view(self.head['w']), self.view(self.head['b']), sums, dbn,
-                                        self.view(self.head['w'], G), self.view(self.head['b'], G), kind, target_value)
-            return self._backward_body(dbn, on_grad_ready)
-        if self.final_pred_activation == 'softmax':  # trained with the soft Dice (loss_dice): through softmax and head in one pass
-            if getattr(self, '_dice', None) is None:
+            return self._backward_body(g_last, on_grad_ready, True)
+        self.grads.zero_()
+        st = self._loss_state
+        if st is None:
+            if self.final_pred_activation == 'softmax':
                 raise RuntimeError('backward() on a softmax head needs loss_dice() first (after predict_probs() the network '
                                    'is frozen: backward_input())')
-            probs, sums, seg, lut = self._dice[:4]
+            raise RuntimeError('backward() needs loss() first (predict() has overwritten the kept activations)')
+        x, stats, gamma, beta, w, b = self._head_in(low, bn)
+        dw, db = self._head_grads()
+        if st.kind == 'linear' and self.nb_labels == 1:
+            # the gradient w.r.t. the last BatchNorm output is rank-1 (dpred[v] * w_head[c]): it is neither stored nor
+            # reduced; head_bwd emits that BN's backward sums and the first ELU backward forms it on the fly
+            off = self.offsets[bn['beta']][0]
+            sums = self.grads[off:off + 2 * bn['C']]
+            if st.head_ab is not None:  # the head kernel of loss() already holds the sums (fuse_head_bwd)
+                ops.head_bwd_from_sums(st.head_ab, gamma, beta, w, dw, db, bn_sums=sums)
+            else:
+                ops.head_bwd(st.dpred, x, stats, gamma, beta, w, None, dw, db, bn_sums=sums)
+            self._pending_bn = _PendingBN(bn, sums)
+            return self._backward_body(None, on_grad_ready, False)
+        dbn = self.buf('dbn_head', list(low.shape))   # every other head writes the gradient w.r.t. the BN output out
+        if st.kind == 'linear':     # K-channel linear head (laplace)
+            ops.head_bwd_multi(st.dpred, x, stats, gamma, beta, w, dbn, dw, db)
+        elif st.kind == 'dice':     # through softmax and head in one pass
             weights = {}
-            if len(self._dice) > 4:   # the weighted Dice: the mask and the class weights of loss_dice()
-                weights = dict(zip(('mask', 'boundary_weights', 'class_weights'), self._dice[4:]))
-            dbn = self.buf('dbn_head', list(low.shape))
-            ops.seg_head_dice_bwd(probs, seg, lut, low, self._stats(bn), self.view(bn['gamma']), self.view(bn['beta']),
-                                  self.view(self.head['w']), sums, dbn, self.view(self.head['w'], G),
-                                  self.view(self.head['b'], G), **weights)
-            return self._backward_body(dbn, on_grad_ready)
-        # the gradient w.r.t. the last BatchNorm output is rank-1 (dpred[v] * w_head[c]): it is neither stored nor
-        # reduced; head_bwd emits that BN's backward sums and the first ELU backward forms it on the fly
-        if self.nb_labels > 1:  # K-channel linear head (laplace): the gradient w.r.t. the BN output is written out
-            dbn = self.buf('dbn_head', list(low.shape))
-            ops.head_bwd_multi(self.dpred, low, self._stats(bn), self.view(bn['gamma']), self.view(bn['beta']),
-                               self.view(self.head['w']), dbn, self.view(self.head['w'], G), self.view(self.head['b'], G))
-            return self._backward_body(dbn, on_grad_ready)
-        off = self.offsets[bn['beta']][0]
-        sums = self.grads[off:off + 2 * bn['C']]
-        if getattr(self, '_head_ab', None) is not None:  # the head kernel of loss() already holds the sums (fuse_head_bwd)
-            ops.head_bwd_from_sums(self._head_ab, self.view(bn['gamma']), self.view(bn['beta']), self.view(self.head['w']),
-                                   self.view(self.head['w'], G), self.view(self.head['b'], G), bn_sums=sums)
-        else:
-            ops.head_bwd(self.dpred, low, self._stats(bn), self.view(bn['gamma']), self.view(bn['beta']),
-                         self.view(self.head['w']), None, self.view(self.head['w'], G), self.view(self.head['b'], G),
-                         bn_sums=sums)
-        self._pending_bn = (bn, sums)
-        self._rank1 = (self.dpred, self.view(self.head['w']))
-        return self._backward_body(None, on_grad_ready)
+            if st.class_weights is not None:   # the weighted Dice: the mask and the class weights of loss_dice()
+                weights = dict(mask=st.mask, boundary_weights=st.boundary_weights, class_weights=st.class_weights)
+            ops.seg_head_dice_bwd(st.probs, st.seg, st.lut, x, stats, gamma, beta, w, st.sums, dbn, dw, db, **weights)
+        else:   # 'logits' (loss_wl2 / loss_cross_entropy): the head kernel forms them again from the kept feature map
+            ops.seg_head_logit_loss_bwd(st.seg, st.lut, x, stats, gamma, beta, w, b, st.sums, dbn, dw, db, st.loss_kind,
+                                        st.target_value)
+        return self._backward_body(dbn, on_grad_ready, False)
 
-    def _backward_body(self, g, on_grad_ready):
+    def _backward_body(self, g, on_grad_ready, frozen):
         L = self.nb_levels
         G = self.grads
-        frozen = self._frozen
         dskips = [None] * L
         for k in range(len(self.dec) - 1, -1, -1):
             d = self.dec[k]
@@ -1030,7 +1015,7 @@ class UNet3D:
             acts = self.saved['dec'][k]
             ps = self._drop_ps is not None
             dacts = self.saved['decd'][k] if ps else acts  # what the consumers of the conv outputs read (per-sample dropout)
-            g = self._bn_backward(g, dacts[-1], d['bn'])
+            g = self._bn_backward(g, dacts[-1], d['bn'], frozen)
             Cs = self.feats[l]
             if d['fold']:
                 skip, lo_bn = self.saved['cat'][k]
@@ -1038,7 +1023,7 @@ class UNet3D:
                 # all convs but the first: regular; the first one through the folded kernels
                 if len(d['convs']) > 1:
                     dz = self._convs_backward(g, None, d['convs'][1:], acts[1:], dacts[0], need_dx=True, tag='d%d' % k,
-                                              elu_below=acts[0], below_conv=d['convs'][0], dacts=dacts[1:])
+                                              frozen=frozen, elu_below=acts[0], below_conv=d['convs'][0], dacts=dacts[1:])
                 else:  # nb_conv_per_level = 1: the folded conv feeds the BatchNorm itself
                     self._join()
                     dz = self._elu_backward(g, acts[0], None, None, conv=d['convs'][0])
@@ -1050,7 +1035,7 @@ class UNet3D:
                     # the unpack kernel leaves the partials it has folded at zero: the buffer is zeroed when it is (re)allocated
                     # or outgrows what has been zeroed so far, not once per call (85 MB of memsets per step at configs[1])
                     base = self._bufs['dwc']
-                    known = getattr(self, '_dwc_zeroed', (None, 0))
+                    known = self._dwc_zeroed
                     dwc_is_zero = known[0] is base and known[1] >= dwc.numel()
                     zeroed = (base, max(dwc.numel(), known[1] if known[0] is base else 0))
 
@@ -1075,7 +1060,7 @@ class UNet3D:
                 self._pb(c0_dgrads, dz, dskips[l], g)
             else:
                 g = self._convs_backward(g, None, d['convs'], acts, self.saved['cat'][k], need_dx=True, tag='d%d' % k,
-                                         dacts=dacts)
+                                         frozen=frozen, dacts=dacts)
                 # g = d(concat)
                 Cl = g.shape[3] - Cs
                 dskips[l], g = ops.upsample_concat_bwd(g, Cs, Cl, dskip=self.buf('dskip%d' % l, self._bshape(l) + [Cs]),
@@ -1101,16 +1086,17 @@ class UNet3D:
                     # pool + BatchNorm + ELU backward re-derives it from the pooled gradient (ops.bn_pool_elu_bwd)
                     ops.bn_maxpool_bwd(g, acts[-1], self._stats(e['bn']), self.view(e['bn']['gamma']),
                                        self.view(e['bn']['beta']), out=False, sums=sums)
-                    self._pending_bn = (e['bn'], sums, 'pooled')
+                    self._pending_bn = _PendingBN(e['bn'], sums, pooled=True)
                 else:
                     g = ops.bn_maxpool_bwd(g, dacts[-1], self._stats(e['bn']), self.view(e['bn']['gamma']),
                                            self.view(e['bn']['beta']), out=self.buf('gpool%d' % l, list(acts[-1].shape)),
                                            sums=sums)
-                    self._pending_bn = (e['bn'], self._zero_sums[:2 * e['bn']['C']] if (frozen and sums is None) else sums)
+                    self._pending_bn = _PendingBN(e['bn'], self._zero_sums[:2 * e['bn']['C']] if (frozen and sums is None)
+                                                  else sums)
             else:
-                g = self._bn_backward(g, dacts[-1], e['bn'])
+                g = self._bn_backward(g, dacts[-1], e['bn'], frozen)
             g = self._convs_backward(g, dskips[l], e['convs'], acts, self.saved['x'][l], need_dx=(l > 0) or frozen,
-                                     tag='e%d' % l, dacts=dacts)
+                                     tag='e%d' % l, frozen=frozen, dacts=dacts)
             if on_grad_ready is not None:
                 self._join()
                 on_grad_ready(self.offsets[e['convs'][0]['w']][0])
@@ -1139,54 +1125,53 @@ class UNet3D:
             torch.cuda.current_stream().wait_stream(self._side_stream)
             self._side_busy = False
 
-    def _bn_backward(self, g, x, bn):
+    def _bn_backward(self, g, x, bn, frozen):
         """pass 1 (channel sums = dbeta | dgamma); pass 2 is fused into the ELU backward of the conv that produced x"""
         if g is None:  # rank-1 head gradient: head_bwd already produced the sums (backward())
             return None
-        if getattr(self, '_frozen', False):
+        if frozen:
             if self.frozen_batch_stats:     # batch-statistics BatchNorm of a frozen network: the full backward, no parameter gradients
                 sums = self._frozen_sums[:2 * bn['C']]
                 sums.zero_()
                 ops.bn_reduce_bwd(g, x, self._stats(bn), sums)
-                self._pending_bn = (bn, sums)
+                self._pending_bn = _PendingBN(bn, sums)
                 return g
             # inference-mode BatchNorm: dx = gamma * invstd * dy, i.e. zero batch sums
-            self._pending_bn = (bn, self._zero_sums[:2 * bn['C']])
+            self._pending_bn = _PendingBN(bn, self._zero_sums[:2 * bn['C']])
             return g
         off = self.offsets[bn['beta']][0]
         sums = self.grads[off:off + 2 * bn['C']]  # [dbeta | dgamma]
         ops.bn_reduce_bwd(g, x, self._stats(bn), sums)
-        self._pending_bn = (bn, sums)
+        self._pending_bn = _PendingBN(bn, sums)
         return g
 
     def _elu_backward(self, g, y, dy2, dbias, conv=None):
         """activation (ELU / ReLU) backward of a conv output y; consumes a pending BN backward (y was the BN input)"""
         out = self.buf('dz', list(y.shape))
         pend, self._pending_bn = self._pending_bn, None
+        # g None: the rank-1 gradient of a one-channel linear head, dpred[v] * w_head[c], formed on the fly
+        rank1 = (self._loss_state.dpred, self.view(self.head['w'])) if g is None else None
         if self._drop_ps is not None:  # per-sample dropout sits between y and its consumer
-            bn_args = head = None
+            bn_args = None
             if pend is not None:
-                assert len(pend) == 2
-                bn_args = (self._stats(pend[0]), self.view(pend[0]['gamma']), pend[1])
-                if g is None:
-                    head = self._rank1
-            return ops.elu_bwd_drop(g, y, self._drop_ps[conv['name']], dy2=dy2, dbias=dbias, out=out, bn=bn_args, head=head,
+                assert not pend.pooled
+                bn_args = (self._stats(pend.bn), self.view(pend.bn['gamma']), pend.sums)
+            return ops.elu_bwd_drop(g, y, self._drop_ps[conv['name']], dy2=dy2, dbias=dbias, out=out, bn=bn_args, head=rank1,
                                     act=self._act)
         if pend is not None:
-            bn, sums = pend[:2]
-            if len(pend) > 2:  # g is the gradient w.r.t. the POOLED tensor: pool + BatchNorm + ELU backward in one pass
+            bn, sums = pend.bn, pend.sums
+            if pend.pooled:  # g is the gradient w.r.t. the POOLED tensor: pool + BatchNorm + ELU backward in one pass
                 return ops.bn_pool_elu_bwd(g, y, self._stats(bn), self.view(bn['gamma']), self.view(bn['beta']), sums,
                                            dy2=dy2, dbias=dbias, out=out, act=self._act)
-            if g is None:  # rank-1 gradient of the head
-                dpred, whead = self._rank1
+            if g is None:
                 assert dy2 is None
-                return ops.bn_elu_bwd_head(dpred, whead, y, self._stats(bn), self.view(bn['gamma']), sums, dbias=dbias,
+                return ops.bn_elu_bwd_head(*rank1, y, self._stats(bn), self.view(bn['gamma']), sums, dbias=dbias,
                                            out=out, act=self._act)
             return ops.bn_elu_bwd(g, y, self._stats(bn), self.view(bn['gamma']), sums, dy2=dy2, dbias=dbias, out=out,
                                   act=self._act)
         return ops.elu_bwd(g, y, dy2=dy2, dbias=dbias, out=out, act=self._act)
 
-    def _convs_backward(self, g, g2, convs, acts, x_in, need_dx, tag, elu_below=None, below_conv=None, dacts=None):
+    def _convs_backward(self, g, g2, convs, acts, x_in, need_dx, tag, frozen, elu_below=None, below_conv=None, dacts=None):
         """g (+g2) = gradient w.r.t. the output of the last conv's ELU. Returns gradient w.r.t. x_in (or None);
         with elu_below = x_in being itself an ELU output (of below_conv), the returned gradient is w.r.t. the pre-activation
         of x_in.  dacts: what the next layer read of each conv output (per-sample dropout: the dropped-out copies)."""
@@ -1198,7 +1183,6 @@ class UNet3D:
             y = acts[j]
             xin = dacts[j - 1] if j > 0 else x_in
             self._join()  # the previous layer's wgrad still reads the buffer dz is about to reuse
-            frozen = getattr(self, '_frozen', False)
             if fused:
                 dz = g
                 if not frozen:

@@ -349,7 +349,9 @@ def test_unet_weighted_dice_loss_and_gradients_vs_autograd(T):
         net.test_loss = loss.clone()
         net.backward()
         # d(loss)/d(posteriors), what single_shot_parity reads as the loss derivative, from what the step kept
-        probs, sums, _, _, mask, bw, c = net._dice
+        st = net._loss_state
+        assert st.kind == 'dice'
+        probs, sums, mask, bw, c = st.probs, st.sums, st.mask, st.boundary_weights, st.class_weights
         assert mask is not None and bw == BETA
         Tn, Bn = sums[:N_SEG] + 1e-7, sums[N_SEG:2 * N_SEG] + 1e-7
         g = -c * wmap.float().cuda().view(-1, N_SEG) * (2 * gt.float().cuda().view(-1, N_SEG) * Bn - 2 * probs * Tn) / (Bn * Bn)
@@ -383,7 +385,7 @@ def test_unet_weighted_dice_loss_and_gradients_vs_autograd(T):
 
 
 def test_default_loss_dice_is_the_step_it_was(T):
-    """loss_dice() with the new parameters at their defaults keeps the 4-tuple of the plain step and its loss bit for bit
+    """loss_dice() with the new parameters at their defaults keeps the record of the plain step and its loss bit for bit
     (deterministic mode), and a weighted call in between does not disturb the next plain one"""
     torch = T
     from synthsr_amd import ops
@@ -393,7 +395,8 @@ def test_default_loss_dice_is_the_step_it_was(T):
     try:
         net = _seg_net(torch)
         a = net.loss_dice(x.cuda(), seg.cuda(), lut.cuda()).clone()
-        assert len(net._dice) == 4
+        st = net._loss_state
+        assert st.kind == 'dice' and st.mask is None and st.class_weights is None
         net.backward()
         ga = net.grads.clone()
         w = net.loss_dice(x.cuda(), seg.cuda(), lut.cuda(), **NET_KW).clone()
@@ -420,7 +423,7 @@ def test_training_segmentation_with_weights_end_to_end(tmp_path):
                                 n_levels=3, unet_feat_count=24, nonlin_shape_factor=.125, bias_shape_factor=.125, lr=1e-3,
                                 verbose=False, deterministic=True, epochs=2, steps_per_epoch=10, fixed_sample=True,
                                 step_losses=rec, dice_class_weights=-1, dice_boundary_weights=.5)
-    assert len(net._dice) == 7 and net._dice[4] is not None
+    assert net._loss_state.kind == 'dice' and net._loss_state.mask is not None
     assert len(rec) == 20 and np.isfinite(rec).all() and rec[19] < rec[0], (rec[0], rec[19])
     ckpt = os.path.join(model_dir, '002.npz')
     assert os.path.exists(ckpt)

@@ -261,7 +261,7 @@ def test_unet_logit_losses_and_gradients_vs_autograd(T, kind):
         z = ((low.reshape(-1, C) - stats[:C]) * torch.rsqrt(stats[C:] + ops.BN_EPS) * net.view(bn['gamma']) + net.view(bn['beta'])) \
             @ net.view(net.head['w']).reshape(C, N_SEG) + net.view(net.head['b'])
         g = gt.float().cuda().view(-1, N_SEG)
-        sums = net._logit_loss[2]
+        sums = net._loss_state.sums
         if kind == 'wl2':
             a = torch.where(g[:, :1] > 0, torch.full_like(g[:, :1], 1e-8), torch.ones_like(g[:, :1]))
             dz = 2 * a * (z - TARGET_VALUE * (2 * g - 1)) / ((sums[1] + 1e-8 * sums[2]) * N_SEG)
@@ -308,9 +308,9 @@ def test_the_two_loss_records_do_not_leak_into_each_other(T):
         for kind in KINDS:
             alone = out(_logit_step(_seg_net(torch), kind, x, seg, lut))
             net = _logit_step(_seg_net(torch), kind, x, seg, lut)
-            assert net._dice is None and net._logit_loss is not None
+            assert net._loss_state.kind == 'logits'
             after = out(_dice_step(net, x, seg, lut))
-            assert net._logit_loss is None and net._dice is not None
+            assert net._loss_state.kind == 'dice'
             assert np.array_equal(after[0], dice_alone[0]) and np.array_equal(after[1], dice_alone[1]), kind
             back = out(_logit_step(net, kind, x, seg, lut))
             assert np.array_equal(back[0], alone[0]) and np.array_equal(back[1], alone[1]), kind
@@ -318,7 +318,7 @@ def test_the_two_loss_records_do_not_leak_into_each_other(T):
         assert ops.deterministic_status() == 1, 'an ordered wait timed out'
         net.training = False
         net.predict_probs(x.cuda())
-        assert net._dice is None and net._logit_loss is None
+        assert net._loss_state is None
         with pytest.raises(RuntimeError):
             net.backward()
     finally:

@@ -374,7 +374,7 @@ def test_predict_labels_vs_float64_oracle(T):
     labels = c['labels'].cuda()
     x = c['x'].cuda()
     got = net.predict_labels(x, labels).clone()
-    assert got.dtype == torch.int32 and tuple(got.shape) == NET_SHAPE and net._dice is None
+    assert got.dtype == torch.int32 and tuple(got.shape) == NET_SHAPE and net._loss_state is None
     _compare_labels('predict_labels', got, c)
     composed = labels[torch.argmax(net.predict_probs(x), dim=1)].reshape(NET_SHAPE)
     sure = c['sure'].cuda()
@@ -401,7 +401,7 @@ def test_segment_volume_flip_average_vs_float64_oracle(T):
     S = c['x'][..., 0].numpy().astype(np.float64)
     seg, post = pred.segment_volume(S, flipping=True, lr_pairs=LR_PAIRS, return_posteriors=True)
     net = pred.net_for(NET_SHAPE)
-    assert net._dice is None
+    assert net._loss_state is None
     assert seg.dtype == np.int32 and seg.shape == NET_SHAPE and post.shape == NET_SHAPE + (5,) and post.dtype == np.float32
     kw = dict(ref=c['avg_ref'], sure=c['avg_sure'], cpu32=c['avg_cpu32'])
     _compare_labels('segment_volume, flipping', torch.from_numpy(seg), c, **kw)

@@ -261,7 +261,7 @@ def test_unet_dice_loss_and_gradients_vs_autograd(T, activation, dropout):
         _dice_step(net, x, seg, lut)
         # what single_shot_parity reads as d(loss)/d(prediction): here the derivative w.r.t. the posteriors, from the kept
         # posteriors and Dice sums (the Dice has no kinks: the oracle's must simply agree)
-        probs, sums, _, _ = net._dice
+        probs, sums = net._loss_state.probs, net._loss_state.sums
         Tn, Bn = sums[:N_SEG] + 1e-7, sums[N_SEG:] + 1e-7
         net.dpred = (-(1.0 / N_SEG) * (2 * gt.float().cuda().view(-1, N_SEG) * Bn - 2 * probs * Tn) / (Bn * Bn)).reshape(-1)
         net.test_stats = (net.bn_true if scales is not None else net.bn_batch).clone()
