@@ -15,6 +15,7 @@
 #include "common.h"
 #include <algorithm>
 #include <cstddef>
+#include <type_traits>
 
 SYN_DET_SETTER(conv3d)
 
@@ -1849,12 +1850,24 @@ __global__ __launch_bounds__(256) void bias_act_kernel(float* __restrict__ y, co
 }
 
 // -------------------------------------------------------------------------------------------- weight gradient
-constexpr int WT0 = 2, WT1 = 4, WT2 = 16;  // voxel tile = 128 voxels = 32 k-steps
-constexpr int WH0 = 4, WH1 = 6, WH2 = 18;
-constexpr int WHV = WH0 * WH1 * WH2;        // 432
-constexpr int WVPX = 434;                   // 434/2 = 217 odd -> rows of [ci][voxel] land on distinct even banks
-constexpr int WTV = WT0 * WT1 * WT2;        // 128
-constexpr int WVPD = 130;                   // 65 odd
+// LDS geometry of a TZ x TY x TX voxel tile of the 16x16x4 weight-gradient kernels: the x halo lies transposed as
+// [ci][halo voxel] rows of VPX floats (the last row all ones: the dbias GEMM row), the dy tile behind it as [co][voxel] rows of
+// VPD floats.  The kernels and launch_wgrad both take strides and sizes from here.
+template <int TZ, int TY, int TX>
+struct WgTileGeom {
+  static constexpr int HZ = TZ + 2, HY = TY + 2, HX = TX + 2, HV = HZ * HY * HX, TV = TZ * TY * TX;
+  static constexpr int VPX = HV + ((HV / 2) % 2 == 0 ? 2 : 0) + (HV % 2);  // even, half of it odd: conflict-free ds_read_b32
+  static constexpr int VPD = TV + 2;
+  static constexpr int PL4 = HY * HX * 6, NJ = (PL4 + 255) / 256;  // float4 per z-plane of a 24-channel halo; columns per thread
+  static_assert((VPX / 2) % 2 == 1 && (VPD / 2) % 2 == 1 && TX % 4 == 0, "LDS strides / k-step rows");
+  static_assert(HY <= 8 && 8 + HX <= 31, "validity bits of a halo column: y from bit 0, x from bit 8, bit 31 = never valid");
+  static constexpr size_t smem(int NT, int CK = 24) { return ((size_t)(CK + 1) * VPX + (size_t)NT * 16 * VPD) * sizeof(float); }
+};
+constexpr int WT0 = 2, WT1 = 4, WT2 = 16;  // voxel tile of conv3d_wgrad_kernel = 128 voxels = 32 k-steps
+using WgGeom = WgTileGeom<WT0, WT1, WT2>;
+constexpr int WH1 = WgGeom::HY, WH2 = WgGeom::HX, WHV = WgGeom::HV, WTV = WgGeom::TV;  // 6, 18, 432, 128
+constexpr int WVPX = WgGeom::VPX;           // 434: 434/2 = 217 odd -> rows of [ci][voxel] land on distinct even banks
+constexpr int WVPD = WgGeom::VPD;           // 130: 65 odd
 
 struct WgExt {
   int up;          // 1: nearest-upsample folding — parity = blockIdx.y % 8, dout is read on that parity sub-lattice of
@@ -2078,127 +2091,47 @@ __global__ __launch_bounds__(256, 2) void conv3d_wgrad_kernel(const float* __res
   }
 }
 
-// ---- VALU-lean weight gradient (CK = 24, Cout % 4 == 0, tensors < 2 GiB).  Same tiling and LDS layout as
-// conv3d_wgrad_kernel; what changes is everything next to the MFMAs (a vector-ALU instruction costs 3-4 cycles of
-// MFMA issue on gfx950, tools/ubench/mfma_issue.hip):
-//  * per-thread staging columns (global byte offset, LDS address, validity bit) are computed once per kernel; per tile
-//    only "offset or out-of-range" selects remain, z-planes / row pairs travel in the scalar soffset of raw buffer
-//    loads, zero padding comes from the hardware range check;
-//  * the 32 k-steps are fully unrolled: LDS reads use immediate offsets and the A/B fragments ping-pong between two
-//    statically indexed register sets (no copies).
-template <int NT, int MS, int NTAPS>
-__global__ __launch_bounds__(256, 2) void conv3d_wgrad_lean_kernel(const float* __restrict__ in,
-                                                                   const float* __restrict__ dout,
-                                                                   float* __restrict__ dw, int D0, int D1, int D2,
-                                                                   int Cin, int Cout, int tiles0, int tiles1, int tiles2,
-                                                                   WgExt ext) {
-  extern __shared__ __attribute__((aligned(16))) float lds[];
-  constexpr int CK = 24;
-  float* lx = lds;                    // [CK + 1][WVPX]; row CK is all ones (the dbias GEMM row)
-  float* ld = lds + (CK + 1) * WVPX;  // [NT*16][WVPD]
-  for (int i = threadIdx.x; i < WVPX; i += 256) lx[CK * WVPX + i] = 1.f;
-  constexpr int MR = NTAPS * CK;
-  constexpr int MTILES = (MR + 15) / 16;
-  constexpr int MTP = (MTILES + MS - 1) / MS;
-  constexpr int MTW = (MTP + 3) / 4;
-  constexpr int C4 = CK / 4;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int li = lane & 15, kq = lane >> 4;
-  static_assert(NTAPS == 27 || MS == 1, "the parity variant does not split the GEMM rows");
-  const int par = (NTAPS == 8) ? (int)(blockIdx.y & 7) : 0;
-  const int cc = (NTAPS == 8) ? (int)(blockIdx.y >> 3) : (int)(blockIdx.y / MS);
-  const int mt0 = (NTAPS == 8) ? 0 : (int)(blockIdx.y % MS) * MTP;
-  const uint32_t tapmask = (NTAPS == 8) ? up_tapmask(par, false) : 0x7FFFFFFu;
-  auto nth_tap = [&](int i) {
-    if (NTAPS == 27) return i;
-    uint32_t m = tapmask;
-    for (int k = 0; k < i; ++k) m &= m - 1;
-    return (int)__builtin_ctz(m);
-  };
-  const int ds = (NTAPS == 8) ? 2 : 1;
-  const int dp0 = (par >> 2) & 1, dp1 = (par >> 1) & 1, dp2 = par & 1;
-  const int co0 = blockIdx.z * NT * 16;
-  constexpr uint32_t OOB = 0x80000000u;
-
-  f32x4 acc[MTW][NT];
-#pragma unroll
-  for (int m = 0; m < MTW; ++m)
-#pragma unroll
-    for (int n = 0; n < NT; ++n) acc[m][n] = (f32x4){0.f, 0.f, 0.f, 0.f};
-
-  // A rows r = (mt0 + wave + 4m)*16 + li -> (tap, ci); the k index of the lane (kq) is folded into the base
-  int a_base[MTW];
-#pragma unroll
-  for (int m = 0; m < MTW; ++m) {
-    int r = (mt0 + wave + 4 * m) * 16 + li;
-    const bool ones = NTAPS == 27 && r == MR;  // row MR: x = 1 at the centre tap -> sum of dout = dbias
-    if (r >= MR) r = MR - 1;
-    const int ti = r / CK, cil = r - ti * CK;
-    const int tap = ones ? 13 : nth_tap(ti);
-    a_base[m] = (ones ? CK : cil) * WVPX + ((tap / 9) * WH1 + (tap / 3) % 3) * WH2 + tap % 3 + kq;
-  }
-  const int b_base = li * WVPD + kq;
-
-  // ---- x halo: 4 z-planes of 6 x 18 voxels x 6 channel quads = 648 float4 per plane, 3 columns per thread
-  constexpr int PL4 = WH1 * WH2 * C4, NJ = (PL4 + 255) / 256, NX = NJ * WH0;
-  const __amdgpu_buffer_rsrc_t rin =
-      __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(in), 0, (int)((int64_t)D0 * D1 * D2 * Cin * 4), 0x00020000);
-  int xrel[NJ], xlds[NJ];
-  uint32_t xmask[NJ];
-#pragma unroll
-  for (int i = 0; i < NJ; ++i) {
-    const int j = tid + 256 * i;
-    const int hy = j / (WH2 * C4), r = j - hy * (WH2 * C4), hx = r / C4, c4 = r - hx * C4;
-    xrel[i] = ((hy * D2 + hx) * Cin + c4 * 4) * 4;
-    xlds[i] = (c4 * 4) * WVPX + hy * WH2 + hx;
-    xmask[i] = j < PL4 ? ((1u << hy) | (1u << (8 + hx))) : 0xFFFFFFFFu;
-  }
-  const int xplane = D1 * D2 * Cin * 4;
-  // ---- dy tile: 8 (z,y) rows of 16 voxels x QN channel quads; row pieces are contiguous in memory
-  constexpr int QN = NT * 4, RQ = 16 * QN, ND = QN / 2;
-  constexpr int P = (QN == 12) ? 3 : 1;      // period of the (row, column) pattern in i
-  constexpr int RPP = 256 * P / RQ;          // rows advanced per period (4, 2, 4)
-  const __amdgpu_buffer_rsrc_t rdo = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<float*>(dout), 0, (int)((int64_t)D0 * D1 * D2 * ds * ds * ds * Cout * 4), 0x00020000);
-  const int dsx = ds * Cout * 4, dsy = ds * (D2 * ds) * Cout * 4;  // byte strides of the dy view
-  const int64_t dsz = (int64_t)ds * (D1 * ds) * (D2 * ds) * Cout * 4;
-  const int dconst = ((dp0 * (D1 * ds) + dp1) * (D2 * ds) + dp2) * Cout * 4;
+// ---- dy staging of conv3d_wgrad_tile_kernel: two structs with the same members.  The constructor builds the per-thread tables
+// (byte offset, LDS address, validity bits) once per kernel, load() fetches the dy tile at (z0, y0, x0) into ND staging registers
+// with raw buffer loads (out-of-volume / masked channel quads get an offset beyond num_records and come back as zeros), commit()
+// writes them transposed into the [co][voxel] LDS tile.
+//
+// WgDyRows, the 2x4x16 tile: 8 (z, y) rows of 16 voxels x QN channel quads; row pieces are contiguous in memory and the (row,
+// column) pattern of thread slot j = tid + 256 i has period P in i, so P table entries serve all ND loads.  It is the one that
+// knows the parity view of the folded convs (NTAPS = 8): low-res grid voxel g -> voxel 2g + parity of a dout of twice the extents.
+template <int NT, int NTAPS>
+struct WgDyRows {
+  static constexpr int QN = NT * 4, RQ = 16 * QN, ND = QN / 2;
+  static constexpr int P = (QN == 12) ? 3 : 1;      // period of the (row, column) pattern in i
+  static constexpr int RPP = 256 * P / RQ;          // rows advanced per period (4, 2, 4)
+  static constexpr int ds = (NTAPS == 8) ? 2 : 1;
+  static constexpr uint32_t OOB = 0x80000000u;
+  __amdgpu_buffer_rsrc_t rdo;
+  int dsx, dsy, dconst;  // byte strides of the dy view, byte offset of the parity origin
+  int64_t dsz;
   int drel[P], dlds[P];
   uint32_t dmask[P];
-#pragma unroll
-  for (int p = 0; p < P; ++p) {
-    const int j = tid + 256 * p;
-    const int row = j / RQ, w = j - row * RQ, vx = w / QN, c4 = w - vx * QN;
-    drel[p] = row * dsy + vx * dsx + (co0 + c4 * 4) * 4;   // row < 4: vz = 0, vy = row
-    dlds[p] = (c4 * 4) * WVPD + row * WT2 + vx;
-    dmask[p] = (co0 + c4 * 4 < Cout) ? ((1u << row) | (1u << (8 + vx))) : 0xFFFFFFFFu;
-  }
+  int D0, D1, D2;
 
-  const int ntiles = tiles0 * tiles1 * tiles2;
-  float4 sx[NX], sd[ND];
-  auto load_tile = [&](int t) {
-    int z0, y0, x0;
-    tile_origin<WT1, WT0, WT2>(t, tiles1, tiles2, z0, y0, x0);
-    // x halo
-    uint32_t bad = 0x80000000u;
+  __device__ __forceinline__ WgDyRows(const float* dout, int D0_, int D1_, int D2_, int Cout, int co0, int par, int tid)
+      : D0(D0_), D1(D1_), D2(D2_) {
+    const int dp0 = (par >> 2) & 1, dp1 = (par >> 1) & 1, dp2 = par & 1;
+    rdo = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(dout), 0,
+                                            (int)((int64_t)D0 * D1 * D2 * ds * ds * ds * Cout * 4), 0x00020000);
+    dsx = ds * Cout * 4;
+    dsy = ds * (D2 * ds) * Cout * 4;
+    dsz = (int64_t)ds * (D1 * ds) * (D2 * ds) * Cout * 4;
+    dconst = ((dp0 * (D1 * ds) + dp1) * (D2 * ds) + dp2) * Cout * 4;
 #pragma unroll
-    for (int h = 0; h < WH1; ++h) bad |= ((unsigned)(y0 - 1 + h) >= (unsigned)D1) ? (1u << h) : 0u;
-#pragma unroll
-    for (int h = 0; h < WH2; ++h) bad |= ((unsigned)(x0 - 1 + h) >= (unsigned)D2) ? (1u << (8 + h)) : 0u;
-    const int yx = (((y0 - 1) * D2 + (x0 - 1)) * Cin + cc * CK) * 4;
-    uint32_t xo[NJ];
-#pragma unroll
-    for (int i = 0; i < NJ; ++i) xo[i] = (xmask[i] & bad) ? OOB : (uint32_t)(xrel[i] + yx);
-#pragma unroll
-    for (int hz = 0; hz < WH0; ++hz) {
-      const int gz = z0 - 1 + hz;
-      const bool pv = (unsigned)gz < (unsigned)D0;
-      const int so = pv ? gz * xplane : 0;
-#pragma unroll
-      for (int i = 0; i < NJ; ++i)
-        sx[hz * NJ + i] = as_f4(__builtin_amdgcn_raw_buffer_load_b128(rin, (int)(pv ? xo[i] : OOB), so, 0));
+    for (int p = 0; p < P; ++p) {
+      const int j = tid + 256 * p;
+      const int row = j / RQ, w = j - row * RQ, vx = w / QN, c4 = w - vx * QN;
+      drel[p] = row * dsy + vx * dsx + (co0 + c4 * 4) * 4;   // row < 4: vz = 0, vy = row
+      dlds[p] = (c4 * 4) * WVPD + row * WT2 + vx;
+      dmask[p] = (co0 + c4 * 4 < Cout) ? ((1u << row) | (1u << (8 + vx))) : 0xFFFFFFFFu;
     }
-    // dy rows
+  }
+  __device__ __forceinline__ void load(int z0, int y0, int x0, float4 (&sd)[ND]) const {
     uint32_t dbad = 0x80000000u;
 #pragma unroll
     for (int h = 0; h < WT1; ++h) dbad |= (y0 + h >= D1) ? (1u << h) : 0u;
@@ -2217,25 +2150,8 @@ __global__ __launch_bounds__(256, 2) void conv3d_wgrad_lean_kernel(const float* 
       const int so = pv ? (int)(dbase + vz * dsz + (int64_t)dvy * dsy) : 0;
       sd[i] = as_f4(__builtin_amdgcn_raw_buffer_load_b128(rdo, (int)vo, so, 0));
     }
-  };
-  if ((int)blockIdx.x < ntiles) load_tile(blockIdx.x);
-
-  for (int t = blockIdx.x; t < ntiles; t += gridDim.x) {
-    __syncthreads();  // previous tile fully consumed
-#pragma unroll
-    for (int i = 0; i < NJ; ++i) {
-      if (i < NJ - 1 || tid + 256 * i < PL4) {
-#pragma unroll
-        for (int hz = 0; hz < WH0; ++hz) {
-          float* d = lx + xlds[i] + hz * (WH1 * WH2);
-          const float4 v = sx[hz * NJ + i];
-          d[0] = v.x;
-          d[WVPX] = v.y;
-          d[2 * WVPX] = v.z;
-          d[3 * WVPX] = v.w;
-        }
-      }
-    }
+  }
+  __device__ __forceinline__ void commit(float* ld, const float4 (&sd)[ND]) const {
 #pragma unroll
     for (int i = 0; i < ND; ++i) {
       const int p = i % P, q = i / P;
@@ -2246,20 +2162,205 @@ __global__ __launch_bounds__(256, 2) void conv3d_wgrad_lean_kernel(const float* 
       d[2 * WVPD] = v.z;
       d[3 * WVPD] = v.w;
     }
+  }
+};
+
+// WgDySlots, the box tiles: TV voxels x QN quads through generic per-thread slots, voxel-major: slot j = tid + 256 i -> (voxel =
+// j / QN, quad = j % QN), one table entry per load.
+template <int TZ, int TY, int TX, int NT>
+struct WgDySlots {
+  using G = WgTileGeom<TZ, TY, TX>;
+  static constexpr int QN = NT * 4, ND = (G::TV * QN + 255) / 256;
+  static constexpr uint32_t OOB = 0x80000000u;
+  __amdgpu_buffer_rsrc_t rdo;
+  int drel[ND], dlds[ND];
+  uint32_t dmask[ND];
+  int D0, D1, D2, Cout, tid;
+
+  __device__ __forceinline__ WgDySlots(const float* dout, int D0_, int D1_, int D2_, int Cout_, int co0, int /*par*/, int tid_)
+      : D0(D0_), D1(D1_), D2(D2_), Cout(Cout_), tid(tid_) {
+    rdo = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(dout), 0, (int)((int64_t)D0 * D1 * D2 * Cout * 4), 0x00020000);
+#pragma unroll
+    for (int i = 0; i < ND; ++i) {
+      const int j = tid + 256 * i;
+      const int vox = j / QN, c4 = j - vox * QN;
+      const int vx = vox % TX, vy = (vox / TX) % TY, vz = vox / (TX * TY);
+      drel[i] = (((vz * D1 + vy) * D2 + vx) * Cout + co0 + c4 * 4) * 4;
+      dlds[i] = (c4 * 4) * G::VPD + vox;
+      dmask[i] = (j < G::TV * QN && co0 + c4 * 4 < Cout) ? ((1u << vz) | (1u << (8 + vy)) | (1u << (16 + vx))) : 0xFFFFFFFFu;
+    }
+  }
+  __device__ __forceinline__ void load(int z0, int y0, int x0, float4 (&sd)[ND]) const {
+    uint32_t dbad = 0x80000000u;
+#pragma unroll
+    for (int h = 0; h < TZ; ++h) dbad |= (z0 + h >= D0) ? (1u << h) : 0u;
+#pragma unroll
+    for (int h = 0; h < TY; ++h) dbad |= (y0 + h >= D1) ? (1u << (8 + h)) : 0u;
+#pragma unroll
+    for (int h = 0; h < TX; ++h) dbad |= (x0 + h >= D2) ? (1u << (16 + h)) : 0u;
+    const int dbase = (((z0 * D1 + y0) * D2 + x0) * Cout) * 4;
+#pragma unroll
+    for (int i = 0; i < ND; ++i)
+      sd[i] = as_f4(__builtin_amdgcn_raw_buffer_load_b128(rdo, (int)((dmask[i] & dbad) ? OOB : (uint32_t)drel[i]), dbase, 0));
+  }
+  __device__ __forceinline__ void commit(float* ld, const float4 (&sd)[ND]) const {
+#pragma unroll
+    for (int i = 0; i < ND; ++i) {
+      if (i < ND - 1 || tid + 256 * i < G::TV * QN) {
+        float* d = ld + dlds[i];
+        const float4 v = sd[i];
+        d[0] = v.x;
+        d[G::VPD] = v.y;
+        d[2 * G::VPD] = v.z;
+        d[3 * G::VPD] = v.w;
+      }
+    }
+  }
+};
+
+// ---- VALU-lean weight gradient on TZ x TY x TX voxel tiles (CK = 24, Cout % 4 == 0, tensors < 2 GiB).  Same GEMM (rows =
+// (tap, ci) + the constant-1 dbias row, N = co, K = voxels) and LDS layout as conv3d_wgrad_kernel; what changes is everything
+// next to the MFMAs (a vector-ALU instruction costs 3-4 cycles of MFMA issue on gfx950, tools/ubench/mfma_issue.hip):
+//  * per-thread staging columns (global byte offset, LDS address, validity bit) are computed once per kernel; per tile
+//    only "offset or out-of-range" selects remain, z-planes / row pairs travel in the scalar soffset of raw buffer
+//    loads, zero padding comes from the hardware range check;
+//  * the TV / 4 k-steps are fully unrolled: LDS reads use immediate offsets and the A/B fragments ping-pong between two
+//    statically indexed register sets (no copies).
+// TX is a multiple of 4, so that the 4 voxels of a k-step share a (z, y) row.  launch_wgrad picks 2x4x16 tiles (also for the
+// 8 taps of a parity, NTAPS = 8), and for the deep levels box tiles that divide the volume exactly: 2x4x16 pads x = 40 / 20 to
+// 48 / 32 (17 / 37 % of the k-steps wasted on zeros), 4x4x8 and 4x4x4 do not.  The tile picks the dy stager.
+template <int NT, int MS, int NTAPS, int TZ, int TY, int TX>
+__global__ __launch_bounds__(256, 2) void conv3d_wgrad_tile_kernel(const float* __restrict__ in,
+                                                                   const float* __restrict__ dout,
+                                                                   float* __restrict__ dw, int D0, int D1, int D2,
+                                                                   int Cin, int Cout, int tiles0, int tiles1, int tiles2,
+                                                                   WgExt ext) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  using G = WgTileGeom<TZ, TY, TX>;
+  using DyStager = std::conditional_t<TX == 16, WgDyRows<NT, NTAPS>, WgDySlots<TZ, TY, TX, NT>>;
+  static_assert(TX != 16 || (TZ == WT0 && TY == WT1), "the row stager is written for the 2x4x16 tile");
+  static_assert(TX == 16 || NTAPS == 27, "only the row stager knows the parity view");
+  constexpr int CK = 24, C4 = CK / 4;
+  constexpr int HZ = G::HZ, HY = G::HY, HX = G::HX, TV = G::TV, VPX = G::VPX, VPD = G::VPD;
+  float* lx = lds;                   // [CK + 1][VPX]; row CK is all ones (the dbias GEMM row)
+  float* ld = lds + (CK + 1) * VPX;  // [NT*16][VPD]
+  for (int i = threadIdx.x; i < VPX; i += 256) lx[CK * VPX + i] = 1.f;
+  constexpr int MR = NTAPS * CK;
+  constexpr int MTILES = (MR + 15) / 16;
+  constexpr int MTP = (MTILES + MS - 1) / MS;
+  constexpr int MTW = (MTP + 3) / 4;
+  static_assert(NTAPS != 27 || MR % 16 != 0, "the dbias row rides in the padding of the last m-tile");
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int li = lane & 15, kq = lane >> 4;
+  static_assert(NTAPS == 27 || MS == 1, "the parity variant does not split the GEMM rows");
+  const int par = (NTAPS == 8) ? (int)(blockIdx.y & 7) : 0;
+  const int cc = (NTAPS == 8) ? (int)(blockIdx.y >> 3) : (int)(blockIdx.y / MS);
+  const int mt0 = (NTAPS == 8) ? 0 : (int)(blockIdx.y % MS) * MTP;
+  const uint32_t tapmask = (NTAPS == 8) ? up_tapmask(par, false) : 0x7FFFFFFu;
+  auto nth_tap = [&](int i) {
+    if (NTAPS == 27) return i;
+    uint32_t m = tapmask;
+    for (int k = 0; k < i; ++k) m &= m - 1;
+    return (int)__builtin_ctz(m);
+  };
+  const int co0 = blockIdx.z * NT * 16;
+  constexpr uint32_t OOB = 0x80000000u;
+
+  f32x4 acc[MTW][NT];
+#pragma unroll
+  for (int m = 0; m < MTW; ++m)
+#pragma unroll
+    for (int n = 0; n < NT; ++n) acc[m][n] = (f32x4){0.f, 0.f, 0.f, 0.f};
+
+  // A rows r = (mt0 + wave + 4m)*16 + li -> (tap, ci); the k index of the lane (kq) is folded into the base
+  int a_base[MTW];
+#pragma unroll
+  for (int m = 0; m < MTW; ++m) {
+    int r = (mt0 + wave + 4 * m) * 16 + li;
+    const bool ones = NTAPS == 27 && r == MR;  // row MR: x = 1 at the centre tap -> sum of dout = dbias
+    if (r >= MR) r = MR - 1;
+    const int ti = r / CK, cil = r - ti * CK;
+    const int tap = ones ? 13 : nth_tap(ti);
+    a_base[m] = (ones ? CK : cil) * VPX + ((tap / 9) * HY + (tap / 3) % 3) * HX + tap % 3 + kq;
+  }
+  const int b_base = li * VPD + kq;
+
+  // ---- x halo: HZ z-planes of HY x HX voxels x 6 channel quads (2x4x16: 648 float4 per plane, 3 columns per thread)
+  constexpr int PL4 = G::PL4, NJ = G::NJ, NX = NJ * HZ;
+  const __amdgpu_buffer_rsrc_t rin =
+      __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(in), 0, (int)((int64_t)D0 * D1 * D2 * Cin * 4), 0x00020000);
+  int xrel[NJ], xlds[NJ];
+  uint32_t xmask[NJ];
+#pragma unroll
+  for (int i = 0; i < NJ; ++i) {
+    const int j = tid + 256 * i;
+    const int hy = j / (HX * C4), r = j - hy * (HX * C4), hx = r / C4, c4 = r - hx * C4;
+    xrel[i] = ((hy * D2 + hx) * Cin + c4 * 4) * 4;
+    xlds[i] = (c4 * 4) * VPX + hy * HX + hx;
+    xmask[i] = j < PL4 ? ((1u << hy) | (1u << (8 + hx))) : 0xFFFFFFFFu;
+  }
+  const int xplane = D1 * D2 * Cin * 4;
+  const DyStager dys(dout, D0, D1, D2, Cout, co0, par, tid);
+
+  const int ntiles = tiles0 * tiles1 * tiles2;
+  float4 sx[NX], sd[DyStager::ND];
+  auto load_tile = [&](int t) {
+    int z0, y0, x0;
+    tile_origin<TY, TZ, TX>(t, tiles1, tiles2, z0, y0, x0);
+    uint32_t bad = 0x80000000u;
+#pragma unroll
+    for (int h = 0; h < HY; ++h) bad |= ((unsigned)(y0 - 1 + h) >= (unsigned)D1) ? (1u << h) : 0u;
+#pragma unroll
+    for (int h = 0; h < HX; ++h) bad |= ((unsigned)(x0 - 1 + h) >= (unsigned)D2) ? (1u << (8 + h)) : 0u;
+    const int yx = (((y0 - 1) * D2 + (x0 - 1)) * Cin + cc * CK) * 4;
+    uint32_t xo[NJ];
+#pragma unroll
+    for (int i = 0; i < NJ; ++i) xo[i] = (xmask[i] & bad) ? OOB : (uint32_t)(xrel[i] + yx);
+#pragma unroll
+    for (int hz = 0; hz < HZ; ++hz) {
+      const int gz = z0 - 1 + hz;
+      const bool pv = (unsigned)gz < (unsigned)D0;
+      const int so = pv ? gz * xplane : 0;
+#pragma unroll
+      for (int i = 0; i < NJ; ++i)
+        sx[hz * NJ + i] = as_f4(__builtin_amdgcn_raw_buffer_load_b128(rin, (int)(pv ? xo[i] : OOB), so, 0));
+    }
+    dys.load(z0, y0, x0, sd);
+  };
+  if ((int)blockIdx.x < ntiles) load_tile(blockIdx.x);
+
+  for (int t = blockIdx.x; t < ntiles; t += gridDim.x) {
+    __syncthreads();  // previous tile fully consumed
+#pragma unroll
+    for (int i = 0; i < NJ; ++i) {
+      if (i < NJ - 1 || tid + 256 * i < PL4) {
+#pragma unroll
+        for (int hz = 0; hz < HZ; ++hz) {
+          float* d = lx + xlds[i] + hz * (HY * HX);
+          const float4 v = sx[hz * NJ + i];
+          d[0] = v.x;
+          d[VPX] = v.y;
+          d[2 * VPX] = v.z;
+          d[3 * VPX] = v.w;
+        }
+      }
+    }
+    dys.commit(ld, sd);
     __syncthreads();
-    if (t + (int)gridDim.x < ntiles) load_tile(t + gridDim.x);  // lands while the 32 k-steps below run
+    if (t + (int)gridDim.x < ntiles) load_tile(t + gridDim.x);  // lands while the k-steps below run
     float aa[2][MTW], bb[2][NT];
 #pragma unroll
-    for (int n = 0; n < NT; ++n) bb[0][n] = ld[b_base + n * 16 * WVPD];
+    for (int n = 0; n < NT; ++n) bb[0][n] = ld[b_base + n * 16 * VPD];
 #pragma unroll
     for (int m = 0; m < MTW; ++m) aa[0][m] = lx[a_base[m]];
 #pragma unroll
-    for (int ks = 0; ks < WTV / 4; ++ks) {
-      constexpr int LAST = WTV / 4 - 1;
+    for (int ks = 0; ks < TV / 4; ++ks) {
+      constexpr int LAST = TV / 4 - 1;
       const int kn = ks < LAST ? ks + 1 : LAST;
-      const int voff = ((kn >> 4) * WH1 + ((kn >> 2) & 3)) * WH2 + 4 * (kn & 3);
+      const int k0 = kn * 4;  // first voxel of the next k-step: (z, y) row and x offset
+      const int voff = ((k0 / (TX * TY)) * HY + (k0 / TX) % TY) * HX + k0 % TX;
 #pragma unroll
-      for (int n = 0; n < NT; ++n) bb[(ks + 1) & 1][n] = ld[b_base + n * 16 * WVPD + kn * 4];
+      for (int n = 0; n < NT; ++n) bb[(ks + 1) & 1][n] = ld[b_base + n * 16 * VPD + kn * 4];
 #pragma unroll
       for (int m = 0; m < MTW; ++m) aa[(ks + 1) & 1][m] = lx[a_base[m] + voff];
       __builtin_amdgcn_sched_barrier(0);
@@ -2297,198 +2398,6 @@ __global__ __launch_bounds__(256, 2) void conv3d_wgrad_lean_kernel(const float* 
       for (int n = 0; n < NT; ++n) {
         const int co = co0 + n * 16 + li;
         if (co < Cout) atomicAdd(&dwp[((size_t)tap * ext.cin_total + ext.ci_off + ci) * Cout + co], acc[m][n][r]);
-      }
-    }
-  }
-}
-
-// ---- weight gradient with small box tiles for the deep levels (40^3: 4x4x8 voxels, 20^3: 4x4x4) ---------------------
-// conv3d_wgrad_lean_kernel's 2x4x16 tiles pad x = 40 / 20 to 48 / 32 (17 / 37 % of the k-steps wasted on zeros).  Same
-// GEMM (rows = (tap, ci) + the constant-1 dbias row, N = co, K = voxels), LDS layouts and unrolled k-steps; the tile is
-// TZ x TY x TX with TX a multiple of 4 so that the 4 voxels of a k-step share a (z, y) row, and the dy tile is staged
-// through generic per-thread slots (voxel-major) instead of the row-pattern of the 16-wide tile.
-template <int NT, int MS, int TZ, int TY, int TX>
-__global__ __launch_bounds__(256, 2) void conv3d_wgrad_box_kernel(const float* __restrict__ in,
-                                                                  const float* __restrict__ dout, float* __restrict__ dw,
-                                                                  int D0, int D1, int D2, int Cin, int Cout, int tiles0,
-                                                                  int tiles1, int tiles2, WgExt ext) {
-  extern __shared__ __attribute__((aligned(16))) float lds[];
-  constexpr int CK = 24, C4 = CK / 4;
-  constexpr int HZ = TZ + 2, HY = TY + 2, HX = TX + 2, HV = HZ * HY * HX, TV = TZ * TY * TX;
-  constexpr int VPX = HV + ((HV / 2) % 2 == 0 ? 2 : 0) + (HV % 2);  // even, half of it odd: conflict-free ds_read_b32
-  constexpr int VPD = TV + 2;
-  static_assert((VPX / 2) % 2 == 1 && (VPD / 2) % 2 == 1 && TX % 4 == 0, "LDS strides / k-step rows");
-  float* lx = lds;                   // [CK + 1][VPX]; row CK = ones (dbias row)
-  float* ld = lds + (CK + 1) * VPX;  // [NT*16][VPD]
-  for (int i = threadIdx.x; i < VPX; i += 256) lx[CK * VPX + i] = 1.f;
-  constexpr int MR = 27 * CK, MTILES = (MR + 15) / 16 + ((MR % 16) == 0 ? 1 : 0);
-  constexpr int MTP = (MTILES + MS - 1) / MS, MTW = (MTP + 3) / 4;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int li = lane & 15, kq = lane >> 4;
-  const int cc = (int)(blockIdx.y / MS);
-  const int mt0 = (int)(blockIdx.y % MS) * MTP;
-  const int co0 = blockIdx.z * NT * 16;
-  constexpr uint32_t OOB = 0x80000000u;
-
-  f32x4 acc[MTW][NT];
-#pragma unroll
-  for (int m = 0; m < MTW; ++m)
-#pragma unroll
-    for (int n = 0; n < NT; ++n) acc[m][n] = (f32x4){0.f, 0.f, 0.f, 0.f};
-  int a_base[MTW];
-#pragma unroll
-  for (int m = 0; m < MTW; ++m) {
-    int r = (mt0 + wave + 4 * m) * 16 + li;
-    const bool ones = r == MR;
-    if (r >= MR) r = MR - 1;
-    const int tap = ones ? 13 : r / CK, cil = r - (r / CK) * CK;
-    a_base[m] = (ones ? CK : cil) * VPX + ((tap / 9) * HY + (tap / 3) % 3) * HX + tap % 3 + kq;
-  }
-  const int b_base = li * VPD + kq;
-
-  // ---- x halo: HZ planes of HY x HX voxels x 6 quads
-  constexpr int PL4 = HY * HX * C4, NJ = (PL4 + 255) / 256, NX = NJ * HZ;
-  const __amdgpu_buffer_rsrc_t rin =
-      __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(in), 0, (int)((int64_t)D0 * D1 * D2 * Cin * 4), 0x00020000);
-  int xrel[NJ], xlds[NJ];
-  uint32_t xmask[NJ];
-#pragma unroll
-  for (int i = 0; i < NJ; ++i) {
-    const int j = tid + 256 * i;
-    const int hy = j / (HX * C4), r = j - hy * (HX * C4), hx = r / C4, c4 = r - hx * C4;
-    xrel[i] = ((hy * D2 + hx) * Cin + c4 * 4) * 4;
-    xlds[i] = (c4 * 4) * VPX + hy * HX + hx;
-    xmask[i] = j < PL4 ? ((1u << hy) | (1u << (12 + hx))) : 0xFFFFFFFFu;
-  }
-  const int xplane = D1 * D2 * Cin * 4;
-  // ---- dy tile: TV voxels x QN quads, slot j = tid + 256 i -> (voxel = j / QN, quad = j % QN)
-  constexpr int QN = NT * 4, ND = (TV * QN + 255) / 256;
-  const __amdgpu_buffer_rsrc_t rdo =
-      __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(dout), 0, (int)((int64_t)D0 * D1 * D2 * Cout * 4), 0x00020000);
-  int drel[ND], dlds[ND];
-  uint32_t dmask[ND];
-#pragma unroll
-  for (int i = 0; i < ND; ++i) {
-    const int j = tid + 256 * i;
-    const int vox = j / QN, c4 = j - vox * QN;
-    const int vx = vox % TX, vy = (vox / TX) % TY, vz = vox / (TX * TY);
-    drel[i] = (((vz * D1 + vy) * D2 + vx) * Cout + co0 + c4 * 4) * 4;
-    dlds[i] = (c4 * 4) * VPD + vox;
-    dmask[i] = (j < TV * QN && co0 + c4 * 4 < Cout) ? ((1u << vz) | (1u << (8 + vy)) | (1u << (16 + vx))) : 0xFFFFFFFFu;
-  }
-
-  const int ntiles = tiles0 * tiles1 * tiles2;
-  float4 sx[NX], sd[ND];
-  auto load_tile = [&](int t) {
-    int z0, y0, x0;
-    tile_origin<TY, TZ, TX>(t, tiles1, tiles2, z0, y0, x0);
-    uint32_t bad = 0x80000000u;
-#pragma unroll
-    for (int h = 0; h < HY; ++h) bad |= ((unsigned)(y0 - 1 + h) >= (unsigned)D1) ? (1u << h) : 0u;
-#pragma unroll
-    for (int h = 0; h < HX; ++h) bad |= ((unsigned)(x0 - 1 + h) >= (unsigned)D2) ? (1u << (12 + h)) : 0u;
-    const int yx = (((y0 - 1) * D2 + (x0 - 1)) * Cin + cc * CK) * 4;
-    uint32_t xo[NJ];
-#pragma unroll
-    for (int i = 0; i < NJ; ++i) xo[i] = (xmask[i] & bad) ? OOB : (uint32_t)(xrel[i] + yx);
-#pragma unroll
-    for (int hz = 0; hz < HZ; ++hz) {
-      const int gz = z0 - 1 + hz;
-      const bool pv = (unsigned)gz < (unsigned)D0;
-      const int so = pv ? gz * xplane : 0;
-#pragma unroll
-      for (int i = 0; i < NJ; ++i)
-        sx[hz * NJ + i] = as_f4(__builtin_amdgcn_raw_buffer_load_b128(rin, (int)(pv ? xo[i] : OOB), so, 0));
-    }
-    uint32_t dbad = 0x80000000u;
-#pragma unroll
-    for (int h = 0; h < TZ; ++h) dbad |= (z0 + h >= D0) ? (1u << h) : 0u;
-#pragma unroll
-    for (int h = 0; h < TY; ++h) dbad |= (y0 + h >= D1) ? (1u << (8 + h)) : 0u;
-#pragma unroll
-    for (int h = 0; h < TX; ++h) dbad |= (x0 + h >= D2) ? (1u << (16 + h)) : 0u;
-    const int dbase = (((z0 * D1 + y0) * D2 + x0) * Cout) * 4;
-#pragma unroll
-    for (int i = 0; i < ND; ++i)
-      sd[i] = as_f4(__builtin_amdgcn_raw_buffer_load_b128(rdo, (int)((dmask[i] & dbad) ? OOB : (uint32_t)drel[i]), dbase, 0));
-  };
-  if ((int)blockIdx.x < ntiles) load_tile(blockIdx.x);
-
-  for (int t = blockIdx.x; t < ntiles; t += gridDim.x) {
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < NJ; ++i) {
-      if (i < NJ - 1 || tid + 256 * i < PL4) {
-#pragma unroll
-        for (int hz = 0; hz < HZ; ++hz) {
-          float* d = lx + xlds[i] + hz * (HY * HX);
-          const float4 v = sx[hz * NJ + i];
-          d[0] = v.x;
-          d[VPX] = v.y;
-          d[2 * VPX] = v.z;
-          d[3 * VPX] = v.w;
-        }
-      }
-    }
-#pragma unroll
-    for (int i = 0; i < ND; ++i) {
-      if (i < ND - 1 || tid + 256 * i < TV * QN) {
-        float* d = ld + dlds[i];
-        const float4 v = sd[i];
-        d[0] = v.x;
-        d[VPD] = v.y;
-        d[2 * VPD] = v.z;
-        d[3 * VPD] = v.w;
-      }
-    }
-    __syncthreads();
-    if (t + (int)gridDim.x < ntiles) load_tile(t + gridDim.x);
-    float aa[2][MTW], bb[2][NT];
-#pragma unroll
-    for (int n = 0; n < NT; ++n) bb[0][n] = ld[b_base + n * 16 * VPD];
-#pragma unroll
-    for (int m = 0; m < MTW; ++m) aa[0][m] = lx[a_base[m]];
-#pragma unroll
-    for (int ks = 0; ks < TV / 4; ++ks) {
-      constexpr int LAST = TV / 4 - 1;
-      const int kn = ks < LAST ? ks + 1 : LAST;
-      const int k0 = kn * 4;  // first voxel of the next k-step: (z, y) row and x offset
-      const int voff = ((k0 / (TX * TY)) * HY + (k0 / TX) % TY) * HX + k0 % TX;
-#pragma unroll
-      for (int n = 0; n < NT; ++n) bb[(ks + 1) & 1][n] = ld[b_base + n * 16 * VPD + kn * 4];
-#pragma unroll
-      for (int m = 0; m < MTW; ++m) aa[(ks + 1) & 1][m] = lx[a_base[m] + voff];
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int m = 0; m < MTW; ++m)
-#pragma unroll
-        for (int n = 0; n < NT; ++n)
-          acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x4f32(aa[ks & 1][m], bb[ks & 1][n], acc[m][n], 0, 0, 0);
-      __builtin_amdgcn_sched_barrier(0);
-    }
-  }
-  const size_t detoff = (size_t)blockIdx.x * ext.det_stride;  // deterministic mode: this workgroup column's own plane
-#pragma unroll
-  for (int m = 0; m < MTW; ++m) {
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      if (wave + 4 * m >= MTP) continue;
-      const int row = (mt0 + wave + 4 * m) * 16 + kq * 4 + r;
-      if (row == MR && ext.dbias && cc == 0) {
-#pragma unroll
-        for (int n = 0; n < NT; ++n) {
-          const int co = co0 + n * 16 + li;
-          if (co < Cout) atomicAdd(&ext.dbias[detoff + co], acc[m][n][r]);
-        }
-      }
-      if (row >= MR) continue;
-      const int tap = row / CK, cil = row - tap * CK;
-      const int ci = cc * CK + cil;
-      if (ci >= Cin) continue;
-#pragma unroll
-      for (int n = 0; n < NT; ++n) {
-        const int co = co0 + n * 16 + li;
-        if (co < Cout) atomicAdd(&dw[detoff + ((size_t)tap * ext.cin_total + ext.ci_off + ci) * Cout + co], acc[m][n][r]);
       }
     }
   }
@@ -3298,62 +3207,54 @@ static int det_finish_impl(const DetRun* d, hipStream_t st) {
   return hipGetLastError() == hipSuccess ? SYNTHSR_OK : SYNTHSR_ELAUNCH;
 }
 
+// 512 workgroups in total = the 2 per CU that fit: every extra workgroup only adds a 27*CK*Cout atomic flush
+inline int wgrad_grid_x(int wgs_per_column, int ntiles) { return std::clamp(512 / wgs_per_column, 1, ntiles); }
+
+// one launch of conv3d_wgrad_tile_kernel on TZ x TY x TX voxel tiles, between the deterministic mode's prepare and finish
+template <int NT, int MS, int NTAPS, int TZ, int TY, int TX>
+int launch_wgrad_tile(const float* in, const float* dout, float* dw, const int s[3], int Cin, int Cout, int64_t dw_elems,
+                      hipStream_t st, WgExt ext) {
+  constexpr auto kern = conv3d_wgrad_tile_kernel<NT, MS, NTAPS, TZ, TY, TX>;
+  constexpr size_t smem = WgTileGeom<TZ, TY, TX>::smem(NT);
+  const int tiles0 = cdiv(s[0], TZ), tiles1 = cdiv(s[1], TY), tiles2 = cdiv(s[2], TX);
+  const int ncc = cdiv(Cin, 24), nco = cdiv(Cout, NT * 16);
+  const int ymul = (NTAPS == 8) ? 8 : MS;
+  const int gx = wgrad_grid_x(ncc * nco * ymul, tiles0 * tiles1 * tiles2);
+  max_dyn_smem<kern>(smem);
+  DetRun det;
+  if (const int rc_ = syn_det_prepare(&det, &dw, &ext.dbias, dw_elems, Cout, gx, st)) return rc_;
+  ext.det_stride = det.stride;
+  hipLaunchKernelGGL(kern, dim3(gx, ncc * ymul, nco), dim3(256), smem, st, in, dout, dw, s[0], s[1], s[2], Cin, Cout, tiles0,
+                     tiles1, tiles2, ext);
+  if (hipGetLastError() != hipSuccess) return SYNTHSR_ELAUNCH;
+  return syn_det_finish(&det, st);
+}
+
 template <int CK, int NT, int MS, int NTAPS>
 int launch_wgrad(const float* in, const float* dout, float* dw, const int s[3], int Cin, int Cout, hipStream_t st,
                  const WgExt& ext0) {
   WgExt ext = ext0;
-  DetRun det;
   const int64_t dw_elems = (NTAPS == 8) ? 8 * ext.dwstride : (int64_t)27 * ext.cin_total * Cout;
-  const int tiles0 = cdiv(s[0], WT0), tiles1 = cdiv(s[1], WT1), tiles2 = cdiv(s[2], WT2);
-  const int ntiles = tiles0 * tiles1 * tiles2;
-  const int ncc = cdiv(Cin, CK), nco = cdiv(Cout, NT * 16);
-  const int ymul = (NTAPS == 8) ? 8 : MS;
-  // 512 workgroups in total = the 2 per CU that fit: every extra workgroup only adds a 27*CK*Cout atomic flush
-  int gx = 512 / (ncc * nco * ymul);
-  if (gx < 1) gx = 1;
-  if (gx > ntiles) gx = ntiles;
-  const size_t smem = ((size_t)(CK + 1) * WVPX + (size_t)NT * 16 * WVPD) * sizeof(float);
   if constexpr (CK == 24) {
     const int dsc = (NTAPS == 8) ? 8 : 1;
     const int64_t xbytes = (int64_t)s[0] * s[1] * s[2] * Cin * 4, dbytes = (int64_t)s[0] * s[1] * s[2] * dsc * Cout * 4;
-    if constexpr (NTAPS == 27) {
-      // small deep levels: box tiles that divide the volume exactly (4x4x8 for x = 40, 4x4x4 for x = 20)
-      const bool div4 = (s[0] % 4) == 0 && (s[1] % 4) == 0 && (s[2] % 4) == 0 && (s[2] % 16) != 0;
-      if (div4 && (Cout % 4) == 0 && xbytes < (1ll << 31) && dbytes < (1ll << 31)) {
-        const bool x8 = (s[2] % 8) == 0;
-        const int tx = x8 ? 8 : 4;
-        const int bt0 = s[0] / 4, bt1 = s[1] / 4, bt2 = s[2] / tx;
-        const int bnt = bt0 * bt1 * bt2;
-        int bgx = 512 / (ncc * nco * ymul);
-        if (bgx < 1) bgx = 1;
-        if (bgx > bnt) bgx = bnt;
-        const int hv = 6 * 6 * (tx + 2), tv = 16 * tx;
-        const int vpx = hv + ((hv / 2) % 2 == 0 ? 2 : 0) + (hv % 2);
-        const size_t bsmem = ((size_t)(CK + 1) * vpx + (size_t)NT * 16 * (tv + 2)) * sizeof(float);
-        if (const int rc_ = syn_det_prepare(&det, &dw, &ext.dbias, dw_elems, Cout, bgx, st)) return rc_;
-        ext.det_stride = det.stride;
-        if (x8) {
-          hipLaunchKernelGGL((conv3d_wgrad_box_kernel<NT, MS, 4, 4, 8>), dim3(bgx, ncc * ymul, nco), dim3(256), bsmem, st, in,
-                             dout, dw, s[0], s[1], s[2], Cin, Cout, bt0, bt1, bt2, ext);
-        } else {
-          hipLaunchKernelGGL((conv3d_wgrad_box_kernel<NT, MS, 4, 4, 4>), dim3(bgx, ncc * ymul, nco), dim3(256), bsmem, st, in,
-                             dout, dw, s[0], s[1], s[2], Cin, Cout, bt0, bt1, bt2, ext);
-        }
-        if (hipGetLastError() != hipSuccess) return SYNTHSR_ELAUNCH;
-        return syn_det_finish(&det, st);
-      }
-    }
     if ((Cout % 4) == 0 && xbytes < (1ll << 31) && dbytes < (1ll << 31)) {
-      constexpr auto lkern = conv3d_wgrad_lean_kernel<NT, MS, NTAPS>;
-      max_dyn_smem<lkern>(smem);
-      if (const int rc_ = syn_det_prepare(&det, &dw, &ext.dbias, dw_elems, Cout, gx, st)) return rc_;
-      ext.det_stride = det.stride;
-      hipLaunchKernelGGL(lkern, dim3(gx, ncc * ymul, nco), dim3(256), smem, st, in, dout, dw, s[0], s[1], s[2], Cin, Cout,
-                         tiles0, tiles1, tiles2, ext);
-      if (hipGetLastError() != hipSuccess) return SYNTHSR_ELAUNCH;
-      return syn_det_finish(&det, st);
+      if constexpr (NTAPS == 27) {
+        // small deep levels: box tiles that divide the volume exactly (4x4x8 for x = 40, 4x4x4 for x = 20)
+        const bool div4 = (s[0] % 4) == 0 && (s[1] % 4) == 0 && (s[2] % 4) == 0 && (s[2] % 16) != 0;
+        const bool x8 = (s[2] % 8) == 0;
+        if (div4 && x8) return launch_wgrad_tile<NT, MS, 27, 4, 4, 8>(in, dout, dw, s, Cin, Cout, dw_elems, st, ext);
+        if (div4) return launch_wgrad_tile<NT, MS, 27, 4, 4, 4>(in, dout, dw, s, Cin, Cout, dw_elems, st, ext);
+      }
+      return launch_wgrad_tile<NT, MS, NTAPS, WT0, WT1, WT2>(in, dout, dw, s, Cin, Cout, dw_elems, st, ext);
     }
   }
+  DetRun det;
+  const int tiles0 = cdiv(s[0], WT0), tiles1 = cdiv(s[1], WT1), tiles2 = cdiv(s[2], WT2);
+  const int ncc = cdiv(Cin, CK), nco = cdiv(Cout, NT * 16);
+  const int ymul = (NTAPS == 8) ? 8 : MS;
+  const int gx = wgrad_grid_x(ncc * nco * ymul, tiles0 * tiles1 * tiles2);
+  const size_t smem = WgGeom::smem(NT, CK);
   constexpr auto kern = conv3d_wgrad_kernel<CK, NT, MS, NTAPS>;
   max_dyn_smem<kern>(smem);
   // planes first: a call that returns SYNTHSR_EWORKSPACE has launched NOTHING (the caller repeats it -- a column sum already

@@ -50,6 +50,14 @@ CASES = [
     _c('lean', 'plain', 'fp32_mfma', 'f32', (5, 6, 18), 24, 48, 'lean'),
     _c('box_x8', 'plain', 'fp32_mfma', 'f32', (4, 8, 8), 48, 96, 'box_x8'),
     _c('box_x4', 'plain', 'fp32_mfma', 'f32', (4, 4, 12), 48, 96, 'box_x4'),
+    # ... the tile kernel's (NT, MS, tile) matrix and its mask edges: NT 1 / MS 1; NT 2 over two input-channel chunks of a partial
+    # range (dbias from chunk 0 only); a masked last output-channel quad on either dy stager; every extent below the 2x4x16 tile
+    _c('lean_nt1', 'plain', 'fp32_mfma', 'f32', (5, 6, 18), 24, 16, 'lean'),
+    _c('lean_nt2_cc2_part', 'plain', 'fp32_mfma', 'f32', (5, 6, 18), 48, 32, 'lean', ci_off=8, cin_total=64),
+    _c('lean_cout20', 'plain', 'fp32_mfma', 'f32', (5, 6, 18), 24, 20, 'lean'),
+    _c('lean_below_tile', 'plain', 'fp32_mfma', 'f32', (1, 3, 7), 24, 48, 'lean'),
+    _c('box_x8_nt2', 'plain', 'fp32_mfma', 'f32', (4, 8, 8), 24, 32, 'box_x8'),
+    _c('box_x4_cout20', 'plain', 'fp32_mfma', 'f32', (4, 4, 12), 24, 20, 'box_x4'),
     _c('p4', 'plain', 'fp32_mfma', 'f32', (5, 6, 18), 48, 24, 'p4'),
     _c('p4_below_tile', 'plain', 'fp32_mfma', 'f32', (3, 5, 7), 24, 24, 'p4'),   # z and x extents below the 4 x 4 x 16 tile
     _c('c2_cin2', 'plain', 'fp32_mfma', 'f32', (6, 5, 17), 2, 24, 'c2', planes=False),
@@ -63,6 +71,7 @@ CASES = [
     # the up-sampled channel range of a folded decoder conv
     _c('up_split', 'up', 'split', 'f32', (5, 7, 9), 32, 48, 'up_split', split=True),
     _c('up_lean', 'up', 'fp32_mfma', 'f32', (3, 2, 3), 24, 48, 'up_lean'),
+    _c('up_lean_nt1_cc2', 'up', 'fp32_mfma', 'f32', (3, 2, 3), 48, 16, 'up_lean'),   # parity view, NT 1, two chunks
     _c('up_generic', 'up', 'fp32_mfma', 'f32', (3, 5, 7), 16, 24, 'up_generic'),
     _c('up_p4', 'up', 'fp32_mfma', 'f32', (64, 48, 56), 24, 24, 'up_p4', f64=False),
     # bf16 (conv_bf16.hip: chunks of 32 / 24 / 8 input channels)
