@@ -793,6 +793,57 @@ int synthsr_sr_ssim3d(const float* pred, const float* truth, const int32_t* mask
                       float inv_range, double* out, float* ssim_map, void* workspace, int64_t workspace_bytes,
                       synthsr_stream_t stream);
 
+/* --- inference volumes: what predict.py does around the U-Net, on the device -------------------------------------------------
+ * fp32 volumes, contiguous, last axis fastest.  Host arguments: shapes, offsets, M, taps, strides, scalars; everything else is
+ * device memory.  Limits of all four calls: every side (source, output, box, destination) 1 .. 1024, 1 <= Cd <= 2 channels,
+ * 0 <= c < Cd, the box [offset, offset + shape) inside the destination (source of the crop).  A NULL required pointer, a
+ * non-finite entry of M, taps, gain, a or b, or anything outside the limits returns SYNTHSR_EINVAL before any launch.  The
+ * library allocates nothing and keeps no state; the same input gives the same bits.
+ *
+ * volume_blur_axis: one axis of scipy.ndimage.gaussian_filter(mode='reflect') on in [shape[0]][shape[1]][shape[2]]:
+ *     out[i] = sum_{t = -r .. r} taps[t + r] in[reflect(i + t)] along `axis` (0, 1 or 2), summed in fp32 in that order, with
+ *     reflect(x): m = x mod 2 n (0 <= m < 2 n), m < n ? m : 2 n - 1 - m  (d c b a | a b c d | d c b a), applied in full, so an
+ *     axis shorter than the radius is right.  taps: 2 r + 1 fp32 values on the HOST, 1 <= radius <= 16.  in and out may not
+ *     overlap (checked).  One launch.
+ * volume_resample: trilinear samples of src [src_shape] written into a box of a channel-last destination,
+ *     dst[(((offset[0] + i) D1 + offset[1] + j) D2 + offset[2] + k) Cd + c] for every (i, j, k) of out_shape, D = dst_shape;
+ *     nothing else of dst is touched.
+ *   coordinates  pos[a] = M[a][0] i + M[a][1] j + M[a][2] k + M[a][3], M [12] row-major 3 x 4, evaluated in double on the device
+ *                (the convention of synthsr_seg_resample_argmax).  Axis permutations and flips are part of M.
+ *   mode         SYNTHSR_RESAMPLE_CLAMP: pos <- clip(pos, 0, n - 1) (volumes.resample_volume through _axis_samples).
+ *                SYNTHSR_RESAMPLE_ZERO_OUTSIDE: the value is 0 unless 0 <= pos[a] <= n[a] - 1 on all three axes
+ *                (volumes.resample_volume_like).
+ *   corners      i0 = min(floor(pos), max(n - 2, 0)), i1 = min(i0 + 1, n - 1), w = pos - i0 rounded to fp32
+ *                (volumes._interp_axis); a (1 - w) + b w in fp32 along axis 2, then 1, then 0.
+ *   minmax       [2], device: the minimum and maximum of the values written (zeros of ZERO_OUTSIDE included), complete when the
+ *                stream reaches the end of the call.  One (min, max) pair per workgroup in the workspace, reduced by a second
+ *                launch: exact, so the same in any order.
+ *   workspace    SYNTHSR_VOLUME_RESAMPLE_WORKSPACE_BYTES of device memory, 4-byte aligned, owned by the caller; its contents need
+ *                no initialisation and mean nothing afterwards.
+ * volume_normalise_pad: over the whole dst [D0][D1][D2][Cd], channel c: inside the box x <- gain * ((x - lo) / (hi - lo)) with
+ *     lo = minmax[0], hi = minmax[1] read on the device and a true division (the maximum maps to exactly gain, the minimum to 0);
+ *     outside the box exact 0, whatever the buffer held.  hi == lo gives 0 inside the box as well: the host path
+ *     (predict.prepare_volume) divides 0 by 0 there and returns NaN.  One launch.
+ * sr_postprocess: out [out_shape] (only that) = clip(a (p + addend[i, j, k]) + b, lo, hi) with p = net[offset + (i, j, k)] of
+ *     net [net_shape], or, with netf (the network's output for the volume flipped along axis 0),
+ *     p = 0.5 net[o0 + i, ..] + 0.5 netf[D0 - 1 - (o0 + i), ..].  addend: NULL, or fp32 at addend + i stride[0] + j stride[1] +
+ *     k stride[2] (strides in elements, >= 1, host), so a box of a larger buffer serves as it lies.  lo <= hi, either may be
+ *     infinite.  predict.postprocess: a = 255, b = 0, [0, 128]; postprocess_hyperfine: a = spread, b = minimum, addend = the
+ *     normalised T1, [0, +inf).  One launch. */
+#define SYNTHSR_RESAMPLE_CLAMP 0
+#define SYNTHSR_RESAMPLE_ZERO_OUTSIDE 1
+#define SYNTHSR_VOLUME_RESAMPLE_WORKSPACE_BYTES 8192
+int synthsr_volume_blur_axis(const float* in, const int* shape, int axis, const float* taps, int radius, float* out,
+                             synthsr_stream_t stream);
+int synthsr_volume_resample(const float* src, const int* src_shape, const double* M, int mode, const int* out_shape, float* dst,
+                            const int* dst_shape, int Cd, const int* offset, int c, float* minmax, void* workspace,
+                            int64_t workspace_bytes, synthsr_stream_t stream);
+int synthsr_volume_normalise_pad(float* dst, const int* dst_shape, int Cd, const int* offset, const int* box_shape, int c,
+                                 const float* minmax, float gain, synthsr_stream_t stream);
+int synthsr_sr_postprocess(const float* net, const float* netf, const int* net_shape, const int* offset, const int* out_shape,
+                           const float* addend, const int64_t* addend_stride, float a, float b, float lo, float hi, float* out,
+                           synthsr_stream_t stream);
+
 /* --- a frozen or inference softmax-headed U-Net in bf16 ------------------------------------------------------------------
  * The feature map x [nvox][C] is bf16 (8-byte aligned: one channel quad per vector load); BatchNorm statistics, gamma / beta,
  * the head's fp32 master weights w / b, posteriors, prev and the Dice sums stay fp32, so the arithmetic on a given bf16 x is

@@ -20,6 +20,9 @@ def build_parser():
     p.add_argument('--ct', action='store_true', help='the inputs are CT scans (clipped to [0, 80] HU first)')
     p.add_argument('--model', default=None, help='weights: Keras .h5 as released with the reference, or .npz checkpoint')
     p.add_argument('--disable_flipping', action='store_true', help='no left-right flip averaging at test time')
+    p.add_argument('--preprocessing', choices=('host', 'device'), default='host',
+                   help='where resampling, normalisation, padding and the post-processing run: numpy on the host (float64, the '
+                        'default) or HIP kernels on the device (float32)')
     p.add_argument('--cpu', action='store_true', help='reference flag; CPU inference is not part of this build')
     p.add_argument('--threads', type=int, default=1, help='reference flag; ignored')
     return p
@@ -32,7 +35,7 @@ def main(argv=None):
     from synthsr_amd.predict import predict
     print('SynthSR prediction' + ('' if args.model is None else ' with the model ' + args.model))
     predict(args.path_images, args.path_predictions, path_model=args.model, ct=args.ct,
-            disable_flipping=args.disable_flipping)
+            disable_flipping=args.disable_flipping, preprocessing=args.preprocessing)
 
 
 if __name__ == '__main__':

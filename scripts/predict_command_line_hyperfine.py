@@ -19,6 +19,9 @@ def build_parser():
                        ('path_t2_images', 'matching T2 scan(s)'), ('path_predictions', 'output file or folder')):
         p.add_argument(name, help=what)
     p.add_argument('--model', default=None, help='weights: Keras .h5 as released with the reference, or .npz checkpoint')
+    p.add_argument('--preprocessing', choices=('host', 'device'), default='host',
+                   help='where resampling, normalisation, padding and the post-processing run: numpy on the host (float64, the '
+                        'default) or HIP kernels on the device (float32)')
     p.add_argument('--cpu', action='store_true', help='reference flag; CPU inference is not part of this build')
     p.add_argument('--threads', type=int, default=1, help='reference flag; ignored')
     return p
@@ -30,7 +33,8 @@ def main(argv=None):
         raise NotImplementedError('--cpu: the MI355X build runs the U-Net through its HIP kernels only')
     from synthsr_amd.predict import predict_hyperfine
     print('SynthSR-hyperfine prediction')
-    predict_hyperfine(args.path_t1_images, args.path_t2_images, args.path_predictions, path_model=args.model)
+    predict_hyperfine(args.path_t1_images, args.path_t2_images, args.path_predictions, path_model=args.model,
+                      preprocessing=args.preprocessing)
     print('All done!')
 
 

@@ -166,6 +166,12 @@ SIGNATURES = {
     'synthsr_sr_moments': (c_int, [_P, _P, _P, POINTER(c_int), _P, _P, c_int64, _S]),
     'synthsr_sr_errors': (c_int, [_P, _P, _P, POINTER(c_int), c_float, c_float, _P, _P, c_int64, _S]),
     'synthsr_sr_ssim3d': (c_int, [_P, _P, _P, POINTER(c_int), c_float, c_float, c_float, _P, _P, _P, c_int64, _S]),
+    'synthsr_volume_blur_axis': (c_int, [_P, POINTER(c_int), c_int, POINTER(c_float), c_int, _P, _S]),
+    'synthsr_volume_resample': (c_int, [_P, POINTER(c_int), POINTER(c_double), c_int, POINTER(c_int), _P, POINTER(c_int), c_int,
+                                        POINTER(c_int), c_int, _P, _P, c_int64, _S]),
+    'synthsr_volume_normalise_pad': (c_int, [_P, POINTER(c_int), c_int, POINTER(c_int), POINTER(c_int), c_int, _P, c_float, _S]),
+    'synthsr_sr_postprocess': (c_int, [_P, _P, POINTER(c_int), POINTER(c_int), POINTER(c_int), _P, POINTER(c_int64), c_float,
+                                       c_float, c_float, c_float, _P, _S]),
     'synthsr_seg_head_fwd_bf16': (c_int, [_P, c_int64, c_int, _P, _P, _P, c_float, _P, _P, c_int, _P, _S]),
     'synthsr_seg_dice_bwd_bf16': (c_int, [_P, _P, c_int64, c_int, c_int, _P, _P, _P, c_int, _P, c_float, _P, _S]),
     'synthsr_seg_head_argmax_bf16': (c_int, [_P, c_int64, c_int, _P, _P, _P, c_float, _P, _P, c_int, _P, _P, _S]),

@@ -23,7 +23,8 @@ SOURCES = [('generator.hip', ['-ffp-contract=off']),
            ('conv_bf16.hip', []),
            ('conv_split.hip', []),
            ('conv3d.hip', []),
-           ('sr_scores.hip', [])]   # last: the objects before it link in the order they always had
+           ('sr_scores.hip', []),
+           ('volume_prep.hip', [])]   # new files go last: the objects before them link in the order they always had
 
 
 def _hipcc():

@@ -1283,6 +1283,147 @@ def seg_resample_argmax(probs, box, M, out_shape, labels, fill_value, want_probs
     return (out, probs_out) if (want_probs or probs_out is not None) else out
 
 
+VOLUME_MAX_SIDE = 1024      # include/synthsr_hip.h: "inference volumes"
+VOLUME_MAX_RADIUS = 16
+VOLUME_RESAMPLE_WORKSPACE_BYTES = 8192
+RESAMPLE_MODES = ('clamp', 'zero_outside')   # index = SYNTHSR_RESAMPLE_*
+
+
+def _volume_f32(what, name, t, dims=(3,)):
+    if not torch.is_tensor(t) or t.dtype != torch.float32 or not t.is_contiguous():
+        raise ValueError('%s takes %s as a contiguous float32 tensor (got %s)' % (what, name, getattr(t, 'dtype', type(t))))
+    if t.dim() not in dims or not all(1 <= int(s) <= VOLUME_MAX_SIDE for s in t.shape[:3]):
+        raise ValueError('%s: %s should be [d0, d1, d2]%s with sides 1 .. %d, got shape %s'
+                         % (what, name, ' or [d0, d1, d2, C]' if 4 in dims else '', VOLUME_MAX_SIDE, tuple(t.shape)))
+    return t
+
+
+def _volume_sides(what, name, shape):
+    shape = tuple(int(s) for s in np.asarray(shape).reshape(-1))
+    if len(shape) != 3 or not all(1 <= s <= VOLUME_MAX_SIDE for s in shape):
+        raise ValueError('%s: %s [d0, d1, d2] with sides 1 .. %d, got %s' % (what, name, VOLUME_MAX_SIDE, shape))
+    return shape
+
+
+def _volume_box(what, buf, channel, offset, shape):
+    """(Cd, offset) of a box of `shape` at `offset` in channel `channel` of buf [D0, D1, D2] or [D0, D1, D2, Cd]"""
+    Cd = int(buf.shape[3]) if buf.dim() == 4 else 1
+    if not 1 <= Cd <= 2 or not 0 <= int(channel) < Cd:
+        raise ValueError('%s: a buffer of 1 or 2 channels and a channel inside it (got %d channels, channel %r)' % (what, Cd, channel))
+    offset = tuple(int(o) for o in np.asarray(offset).reshape(-1))
+    if len(offset) != 3 or not all(0 <= offset[a] <= int(buf.shape[a]) - shape[a] for a in range(3)):
+        raise ValueError('%s: the box of shape %s at offset %s does not lie inside the buffer %s'
+                         % (what, shape, offset, tuple(buf.shape[:3])))
+    return Cd, offset
+
+
+def volume_blur_axis(x, axis, taps, out=None):
+    """One axis of scipy.ndimage.gaussian_filter(mode='reflect') on a float32 volume [n0, n1, n2]: out[i] = sum_t taps[t + r]
+    x[reflect(i + t)] along `axis`.  taps: 2 r + 1 values (host; volumes.gaussian_taps), 1 <= r <= 16.  out may not be x."""
+    _volume_f32('volume_blur_axis', 'x', x)
+    if axis not in (0, 1, 2):
+        raise ValueError('volume_blur_axis: axis is 0, 1 or 2 (got %r)' % (axis,))
+    taps = np.ascontiguousarray(np.asarray(taps, dtype=np.float32).reshape(-1))
+    r = (len(taps) - 1) // 2
+    if len(taps) != 2 * r + 1 or not 1 <= r <= VOLUME_MAX_RADIUS or not np.all(np.isfinite(taps)):
+        raise ValueError('volume_blur_axis: taps are 2 r + 1 finite values with 1 <= r <= %d (got %d values)'
+                         % (VOLUME_MAX_RADIUS, len(taps)))
+    if out is None:
+        out = torch.empty_like(x)
+    _volume_f32('volume_blur_axis', 'out', out)
+    if out.shape != x.shape or out.device != x.device or out.data_ptr() == x.data_ptr():
+        raise ValueError('volume_blur_axis: out should be another float32 volume of x\'s shape on its device')
+    _lib.check(_L().synthsr_volume_blur_axis(_lib.ptr(x), _lib.i3(x.shape), int(axis),
+                                             taps.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), r, _lib.ptr(out), _lib.stream()),
+               'volume_blur_axis')
+    return out
+
+
+def volume_resample(src, M, out_shape, mode='clamp', out=None, offset=(0, 0, 0), channel=0, minmax=None, workspace=None):
+    """(out, minmax): trilinear samples of the float32 volume src [s0, s1, s2] at pos = M (i, j, k, 1) for every voxel (i, j, k) of
+    out_shape, written to out[offset + (i, j, k)] (out [D0, D1, D2]) or out[offset + (i, j, k), channel] (out [D0, D1, D2, Cd],
+    Cd <= 2); the rest of out is left alone.  M: 3 x 4 (or 4 x 4) float64 on the host.  mode 'clamp': positions are clipped to the
+    source grid (volumes.resample_volume); 'zero_outside': 0 for positions outside it (volumes.resample_volume_like).  minmax:
+    float32 [2] on the device, the minimum and maximum of what was written.  out=None: a new volume of out_shape."""
+    what = 'volume_resample'
+    _volume_f32(what, 'src', src)
+    if mode not in RESAMPLE_MODES:
+        raise ValueError('%s: mode is one of %s (got %r)' % (what, RESAMPLE_MODES, mode))
+    out_shape = _volume_sides(what, 'out_shape', out_shape)
+    M = np.asarray(M, dtype=np.float64)
+    if M.shape not in ((3, 4), (4, 4)) or not np.all(np.isfinite(M)):
+        raise ValueError('%s: M should be a finite 3 x 4 (or 4 x 4) matrix' % what)
+    M = np.ascontiguousarray(M[:3])
+    if out is None:
+        out = torch.empty(out_shape, dtype=torch.float32, device=src.device)
+    _volume_f32(what, 'out', out, dims=(3, 4))
+    Cd, offset = _volume_box(what, out, channel, offset, out_shape)
+    if minmax is None:
+        minmax = torch.empty(2, dtype=torch.float32, device=src.device)
+    if minmax.dtype != torch.float32 or minmax.numel() != 2:
+        raise ValueError('%s: minmax should hold 2 float32 values' % what)
+    if workspace is None:
+        workspace = torch.empty(VOLUME_RESAMPLE_WORKSPACE_BYTES, dtype=torch.uint8, device=src.device)
+    if workspace.dtype != torch.uint8 or workspace.numel() < VOLUME_RESAMPLE_WORKSPACE_BYTES or workspace.data_ptr() % 4:
+        raise ValueError('%s: the workspace should be a 4-byte aligned uint8 tensor of at least %d bytes'
+                         % (what, VOLUME_RESAMPLE_WORKSPACE_BYTES))
+    if not (out.device == minmax.device == workspace.device == src.device):
+        raise ValueError('%s: src, out, minmax and the workspace should be on one device' % what)
+    _lib.check(_L().synthsr_volume_resample(_lib.ptr(src), _lib.i3(src.shape), M.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+                                            RESAMPLE_MODES.index(mode), _lib.i3(out_shape), _lib.ptr(out), _lib.i3(out.shape[:3]),
+                                            Cd, _lib.i3(offset), int(channel), _lib.ptr(minmax), _lib.ptr(workspace),
+                                            workspace.numel(), _lib.stream()), what)
+    return out, minmax
+
+
+def volume_normalise_pad(out, offset, box_shape, minmax, gain=1.0, channel=0):
+    """In place on out [D0, D1, D2] or channel `channel` of out [D0, D1, D2, Cd]: x <- gain (x - lo) / (hi - lo) inside the box of
+    box_shape at offset, with (lo, hi) = minmax (float32 [2] on the device: volume_resample's), exact 0 outside it whatever the
+    buffer held.  hi == lo gives 0 everywhere (the host path gives NaN)."""
+    what = 'volume_normalise_pad'
+    _volume_f32(what, 'out', out, dims=(3, 4))
+    box_shape = _volume_sides(what, 'box_shape', box_shape)
+    Cd, offset = _volume_box(what, out, channel, offset, box_shape)
+    if not torch.is_tensor(minmax) or minmax.dtype != torch.float32 or minmax.numel() != 2 or minmax.device != out.device:
+        raise ValueError('%s: minmax should hold 2 float32 values on the buffer\'s device' % what)
+    if not np.isfinite(gain):
+        raise ValueError('%s: gain should be finite (got %r)' % (what, gain))
+    _lib.check(_L().synthsr_volume_normalise_pad(_lib.ptr(out), _lib.i3(out.shape[:3]), Cd, _lib.i3(offset), _lib.i3(box_shape),
+                                                 int(channel), _lib.ptr(minmax), float(gain), _lib.stream()), what)
+    return out
+
+
+def sr_postprocess(net, offset, shape, netf=None, addend=None, a=1.0, b=0.0, lo=-np.inf, hi=np.inf, out=None):
+    """out [shape] = clip(a (p + addend) + b, lo, hi) on the box of `shape` at `offset` of the network output net [D0, D1, D2]:
+    p = net, or with netf (the output for the volume flipped along axis 0) p = 0.5 net + 0.5 flip0(netf).  addend: None, or a
+    float32 tensor of `shape`, any positive strides (a box of a larger buffer as it lies)."""
+    what = 'sr_postprocess'
+    _volume_f32(what, 'net', net)
+    shape = _volume_sides(what, 'shape', shape)
+    _, offset = _volume_box(what, net, 0, offset, shape)
+    if netf is not None:
+        _volume_f32(what, 'netf', netf)
+        if netf.shape != net.shape or netf.device != net.device:
+            raise ValueError('%s: netf should have net\'s shape and device' % what)
+    strides = None
+    if addend is not None:
+        if (not torch.is_tensor(addend) or addend.dtype != torch.float32 or tuple(addend.shape) != shape
+                or addend.device != net.device or min(addend.stride()) < 1):
+            raise ValueError('%s: addend should be a float32 tensor of shape %s with positive strides on net\'s device' % (what, shape))
+        strides = (ctypes.c_int64 * 3)(*addend.stride())
+    if not all(np.isfinite(v) for v in (a, b)) or not lo <= hi:
+        raise ValueError('%s: a and b finite and lo <= hi (got a %r, b %r, [%r, %r])' % (what, a, b, lo, hi))
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=net.device)
+    _volume_f32(what, 'out', out)
+    if tuple(out.shape) != shape or out.device != net.device:
+        raise ValueError('%s: out should be a float32 volume of shape %s on net\'s device' % (what, shape))
+    _lib.check(_L().synthsr_sr_postprocess(_lib.ptr(net), _lib.ptr(netf), _lib.i3(net.shape), _lib.i3(offset), _lib.i3(shape),
+                                           None if addend is None else ctypes.c_void_p(addend.data_ptr()), strides, float(a),
+                                           float(b), float(lo), float(hi), _lib.ptr(out), _lib.stream()), what)
+    return out
+
+
 def adam_step(p, g, m, v, lr_t, beta1=0.9, beta2=0.999, eps=1e-7, grad_scale=1.0):
     lib = _L()
     _lib.check(lib.synthsr_adam_step(_lib.ptr(p), _lib.ptr(g), _lib.ptr(m), _lib.ptr(v), p.numel(), float(lr_t),

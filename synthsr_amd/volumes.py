@@ -189,6 +189,67 @@ def resample_volume_like(vol_ref, aff_ref, vol_flo, aff_flo, interpolation='line
     return out.reshape(shape)
 
 
+MAX_TAPS_RADIUS = 16   # include/synthsr_hip.h: synthsr_volume_blur_axis
+
+
+def gaussian_taps(sigma):
+    """The taps scipy.ndimage.gaussian_filter1d(sigma) applies (truncate 4: radius int(4 sigma + 0.5), normalised in float64), as
+    float32 [2 radius + 1], for ops.volume_blur_axis.  A radius beyond what that kernel takes raises ValueError."""
+    sigma = float(sigma)
+    radius = int(4.0 * sigma + 0.5)
+    if radius > MAX_TAPS_RADIUS:
+        raise ValueError('a blur of sigma %g voxels has radius %d; the device path takes at most %d (voxels below about 1/16 of '
+                         'the target size): use the host path (preprocessing=\'host\')' % (sigma, radius, MAX_TAPS_RADIUS))
+    x = np.arange(-radius, radius + 1)
+    phi = np.exp(-0.5 / (sigma * sigma) * x ** 2) if radius > 0 else np.ones(1)
+    return (phi / phi.sum()).astype(np.float32)
+
+
+def resample_plan(shape, aff, new_vox_size=(1.0, 1.0, 1.0)):
+    """What resample_volume(volume, aff, new_vox_size) followed by align_volume_to_ref(.., aff_ref=identity) do to a volume of
+    `shape`, as one matrix.  Returns (sigmas, M, out_shape, aff_ras):
+      sigmas     per axis of the INPUT volume, the Gaussian resample_volume smooths it with first (0: none);
+      M          3 x 4 float64: voxel (i, j, k) of the re-oriented result samples the smoothed input at M (i, j, k, 1), clipped to
+                 the input grid - the clamped positions of _axis_samples, with the permutation and the flips of
+                 align_volume_to_ref folded in;
+      out_shape, aff_ras   shape and affine of that result, from the expressions of the two functions themselves."""
+    shape = tuple(int(s) for s in shape)
+    if len(shape) != 3:
+        raise ValueError('resample_plan takes the shape of a 3-D volume (got %s)' % (shape,))
+    aff = np.asarray(aff, dtype=np.float64)
+    vox = np.sqrt(np.sum(aff * aff, axis=0))[:-1]                      # as resample_volume
+    factor = vox / np.array(new_vox_size, dtype=np.float64)
+    sigmas = np.where(factor > 1, 0.0, 0.25 / factor)
+    for s in sigmas:
+        gaussian_taps(s)                                                # raises for a radius the device path does not take
+    samples = [_axis_samples(shape[ax], factor[ax]) for ax in range(3)]
+    aff2 = aff.copy()
+    aff2[:3, :3] = aff2[:3, :3] / factor[None, :]
+    aff2[:3, 3] = aff2[:3, 3] - aff2[:3, :3] @ (0.5 * (factor - 1.0))
+    # align_volume_to_ref itself, on a volume that costs nothing, for the shape and the affine
+    ghost = np.broadcast_to(np.zeros(1), tuple(len(p) for p in samples))
+    ghost, aff_ras = align_volume_to_ref(ghost, aff2, aff_ref=np.eye(4), return_aff=True, n_dims=3, return_copy=False)
+    # its permutation and flips for M: result axis w carries input axis frm[w], reversed where the column points against RAS
+    frm = get_ras_axes(aff2, n_dims=3)
+    moved = aff2[:, frm]
+    M = np.zeros((3, 4))
+    for w in range(3):
+        a = int(frm[w])
+        start = -(factor[a] - 1.0) / (2.0 * factor[a])                  # as _axis_samples (before its clip)
+        step = 1.0 / factor[a]
+        if moved[w, w] < 0:                                             # sum(aff_new[:3, :3] * eye, axis=0)[w] < 0
+            M[a, w], M[a, 3] = -step, start + step * (len(samples[a]) - 1)
+        else:
+            M[a, w], M[a, 3] = step, start
+    return sigmas, M, tuple(int(s) for s in ghost.shape), aff_ras
+
+
+def resample_like_matrix(aff_ref, aff_flo):
+    """3 x 4 float64: reference voxel index -> floating voxel coordinates, the matrix of resample_volume_like"""
+    T = np.linalg.inv(np.asarray(aff_flo, dtype=np.float64)) @ np.asarray(aff_ref, dtype=np.float64)
+    return np.ascontiguousarray(T[:3])
+
+
 def rescale_volume(volume, new_min=0, new_max=255, min_percentile=2, max_percentile=98, use_positive_only=False):
     """ext/lab2im/edit_volumes.py:148-176: clip to the [min_percentile, max_percentile] intensities (of the positive
     voxels only if use_positive_only) and map that range linearly onto [new_min, new_max]; a constant volume gives zeros"""
